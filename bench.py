@@ -10,11 +10,17 @@ bf-aligned block range of an N x size blob (weak scaling, no data-path
 collective); the level-1 refs (64 B per 16 GiB) are gathered once per step
 and rank 0 builds the root.
 
-Prints ONE JSON line (rank 0).  Extra objects: roofline (dominant kernel,
-HIP events on the launch stream), cpu_baseline (the oracle on host cores),
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the
+steps and prints the line; --dump-outputs DIR also writes what the last step
+computed (root ref, size / block size / Posts, a fixed sample of the ctext)
+as DIR/<name>.npy.  With --full the line carries extra objects, each from
+runs of its own after the timed steps: roofline (dominant kernel, HIP events
+on the launch stream), cpu_baseline (the oracle on host cores),
 host_round_trip (host memory -> GPU -> host ctext + refs), valu (second
-roofline).  Data is synthetic: a splitmix64 byte stream generated on the GPU
-(glfsx_fill_splitmix_device).  Only the cpu_baseline leg touches oracle/.
+roofline), config2, small_blobs, config4_end_to_end, concat and the PostBlob
+latency / concurrency legs.  Data is synthetic: a splitmix64 byte stream
+generated on the GPU (glfsx_fill_splitmix_device), the same bytes for the
+same arguments.  Only the cpu_baseline leg touches oracle/.
 """
 from __future__ import annotations
 
@@ -61,8 +67,15 @@ def parse(argv=None):
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--no-ctext", action="store_true",
                    help="do not write ctext (NOT the headline configuration)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the extra legs (roofline, CPU "
+                        "baselines, host round trip, configs 2 and 4, PostBlob latency); a "
+                        "plain run times the headline only")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip roofline/cpu/host legs (profiling runs)")
+                   help="skip the extra legs even with --full (a plain run has none)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed (root ref, "
+                        "post count, a fixed seeded sample of the ctext) as DIR/<name>.npy")
     p.add_argument("--cpu-sample-mib", type=int, default=3072)
     p.add_argument("--host-rt-gib", type=float, default=4.0)
     p.add_argument("--rehearse", action="store_true",
@@ -99,6 +112,47 @@ def plan_devices(gpus: int, world: int, local: int, ndev: int, rehearse: bool):
         raise ValueError(f"--gpus {gpus} but only {ndev} GPU(s) visible "
                          "(--rehearse shares devices round-robin)")
     return ("one_process" if gpus > 1 else "single"), [k % ndev for k in range(gpus)]
+
+
+DUMP_BUDGET = 8 * MIB          # ctext bytes sampled in all (float32 on disk: 32 MiB)
+DUMP_CHUNK = 64 << 10
+
+
+def ctext_sample(torch, ctext, part, parts):
+    """A fixed sample of one part's ctext for --dump-outputs: its first and
+    last DUMP_CHUNK bytes and chunks at offsets drawn from a generator seeded
+    by the part's number (the same offsets for the same arguments), or every
+    byte when the part is no larger than its share of DUMP_BUDGET.  float32,
+    one value per byte, in offset order."""
+    import numpy as np
+    n = ctext.numel()
+    share = DUMP_BUDGET // parts
+    if n <= share:
+        return ctext.cpu().numpy().astype(np.float32)
+    k = share // DUMP_CHUNK
+    offs = np.random.default_rng(0x676C6673 + part).integers(0, n - DUMP_CHUNK, size=k - 2)
+    offs = sorted({0, n - DUMP_CHUNK, *(int(o) for o in offs)})
+    got = torch.cat([ctext[o:o + DUMP_CHUNK] for o in offs])
+    return got.cpu().numpy().astype(np.float32)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 or float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def root_arrays(ref, size, block_size, posts):
+    """What a Create hands back besides the ctext: the root's 64 ref bytes,
+    and its size, block size and the number of Posts."""
+    import numpy as np
+    shape = [size, block_size] + ([] if posts is None else [posts])
+    return {"root_ref": np.frombuffer(bytes(ref), dtype=np.uint8).astype(np.float32),
+            "root_size_bs_posts": np.array(shape, dtype=np.float64)}
 
 
 def main():
@@ -195,6 +249,17 @@ def main():
     ms = dt / args.steps * 1e3
     gibs = total / GIB * args.steps / dt
 
+    if args.dump_outputs and args.steps > 0:
+        arrays = {}
+        if rank == 0 and world == 1:
+            arrays = root_arrays(root.ref, root.size, root.block_size, n_posts.value)
+        elif rank == 0:
+            arrays = root_arrays(root_ref[0][:64], total, bs, None)
+        if ctext is not None:
+            name = "ctext_sample" if world == 1 else f"ctext_sample_rank{rank}"
+            arrays[name] = ctext_sample(torch, ctext, rank, world)
+        dump_outputs(args.dump_outputs, arrays)
+
     out = {
         "metric": "GiB/s hashed, device-resident 1 MiB chunks, bigblob write; 1/2/4/8 MI355X",
         "value": round(gibs, 2),
@@ -221,7 +286,7 @@ def main():
                            "every k_pass workgroup, glfsx_clock_probe); peak 2.4",
     }
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if rank == 0:
             out["roofline"], out["valu"] = roofline(torch, N, data, ctext, per, bs, stream, sp,
                                                     step_ms=ms, total_bytes=per)
@@ -414,7 +479,13 @@ def main_one_process(args, devs, host_node=None):
                                   "nodes on its device, then the levels >= 2 on devs[0] (HIP "
                                   "events on the stream that ran them)"},
     }
-    if not args.no_extras:
+    if args.dump_outputs and args.steps > 0:
+        arrays = root_arrays(root.ref, root.size, root.block_size, posts.value)
+        if not args.no_ctext:
+            for k, c in enumerate(cts):
+                arrays[f"ctext_sample_part{k}"] = ctext_sample(torch, c, k, nd)
+        dump_outputs(args.dump_outputs, arrays)
+    if args.full and not args.no_extras:
         stream = torch.cuda.Stream(device=home)
         sp = ctypes.c_void_p(stream.cuda_stream)
         out["roofline"], out["valu"] = roofline(torch, N, bufs[0], cts[0], per, bs, stream, sp,

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 OUT=${1:-gpurun_out/prof_r5}
 mkdir -p $OUT
 B="python bench.py --no-extras --steps 3 --warmup 1"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o run -- python bench.py > $OUT/bench.json 2> $OUT/trace.log || exit $?
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o run -- python bench.py --full > $OUT/bench.json 2> $OUT/trace.log || exit $?
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace -f csv -d $OUT/fetch -o run -- $B > $OUT/fetch.log 2>&1 || exit $?
 timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace -f csv -d $OUT/write -o run -- $B > $OUT/write.log 2>&1 || exit $?
 timeout -s KILL 200 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM SQ_INSTS_LDS SQ_BUSY_CYCLES --kernel-trace -f csv -d $OUT/sq -o run -- $B > $OUT/sq.log 2>&1 || exit $?

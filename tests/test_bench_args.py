@@ -69,6 +69,56 @@ def test_cpu_baseline_cores_are_labelled(monkeypatch):
     assert info["sched_affinity"] == aff and info["nproc"] == os.cpu_count()
 
 
+def test_plain_run_has_no_extra_legs():
+    """A plain run times the headline only: the extra legs (rooflines, CPU
+    baselines, host round trip, configs 2 and 4, ...) are behind --full in
+    both modes, off by default; --no-extras still turns them off."""
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None and a.no_extras is False
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3", "--full",
+                     "--dump-outputs", "d"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (True, "d", 7, 3)
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert src.count("if args.full and not args.no_extras:") == 2     # both modes
+    assert "if not args.no_extras:" not in src
+
+
+def test_ctext_sample_is_fixed_and_bounded():
+    """--dump-outputs samples a large ctext at offsets fixed by the part's
+    number: the same bytes every time, first and last chunk included, within
+    the part's share of the budget; a small ctext is written whole."""
+    import numpy as np
+    import torch
+    n = 3 * bench.DUMP_BUDGET + 12345
+    host = np.random.default_rng(1).integers(0, 256, n, dtype=np.uint8)
+    ct = torch.from_numpy(host)
+    for parts in (1, 2):
+        a = bench.ctext_sample(torch, ct, 0, parts)
+        assert a.dtype == np.float32 and a.size <= bench.DUMP_BUDGET // parts
+        assert a.size >= bench.DUMP_BUDGET // parts - 2 * bench.DUMP_CHUNK
+        assert np.array_equal(a, bench.ctext_sample(torch, ct, 0, parts))
+        c = bench.DUMP_CHUNK
+        assert np.array_equal(a[:c], host[:c]) and np.array_equal(a[-c:], host[-c:])
+    assert not np.array_equal(bench.ctext_sample(torch, ct, 0, 2),
+                              bench.ctext_sample(torch, ct, 1, 2))
+    small = bench.ctext_sample(torch, ct[:bench.DUMP_BUDGET], 0, 1)
+    assert np.array_equal(small, host[:bench.DUMP_BUDGET])
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import numpy as np
+    arrays = bench.root_arrays(bytes(range(64)), 64 << 30, 1 << 20, 65541)
+    d = tmp_path / "a" / "b"
+    bench.dump_outputs(str(d), arrays)
+    assert sorted(os.listdir(d)) == ["root_ref.npy", "root_size_bs_posts.npy"]
+    ref = np.load(d / "root_ref.npy")
+    assert ref.dtype == np.float32 and ref.tolist() == list(range(64))
+    shape = np.load(d / "root_size_bs_posts.npy")
+    assert shape.dtype == np.float64 and shape.tolist() == [64 << 30, 1 << 20, 65541]
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(d), {"x": np.zeros(4, dtype=np.uint8)})
+
+
 def test_fused_reruns_fail_the_run():
     """the bench line reports re-runs of failed one-launch
     split posts per timed leg and a non-zero count fails the run."""
