@@ -1,5 +1,9 @@
 // kernels.h -- internal interface between the host runtime (glfsx.cpp) and the
-// gfx950 kernels (post_kernels.hip).  Not part of the C-ABI.
+// gfx950 kernels: post_kernels.hip (the launches, with its fragments b3_arx.h,
+// pass_kernels.h, quad_kernels.h, one_kernels.h, small_kernels.h and
+// read_kernels.h holding the kernels by family), tree_kernels.hip and
+// xof_kernels.hip (device_common.h: definitions the three share).  Not part
+// of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

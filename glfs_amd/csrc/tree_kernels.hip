@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_common.h"
 #include "kernels.h"
 
 namespace glfsx {
@@ -208,15 +209,6 @@ __device__ void dec(S &k, uint64_t v) {
   } else {
     while (c) k.put(t[--c]);
   }
-}
-
-// Lower-case hex digits of bytes b0, b1 (bits 0-15 of x) as four ASCII bytes
-// in output order (hi(b0) lo(b0) hi(b1) lo(b1)), little-endian.
-__device__ __forceinline__ uint32_t hex4(uint32_t x) {
-  const uint32_t n = ((x >> 4) & 0xFu) | ((x & 0xFu) << 8) |
-                     ((x >> 12) & 0xFu) << 16 | ((x >> 8) & 0xFu) << 24;
-  const uint32_t ge10 = ((n + 0x06060606u) >> 4) & 0x01010101u;  // nibble >= 10
-  return n + 0x30303030u + ge10 * 39u;  // '0' + n, or 'a' - 10 + n
 }
 
 // "<64 hex digits>" of the 32 bytes at x (one 64-B ref holds two: aligned
@@ -445,13 +437,6 @@ __global__ __launch_bounds__(kHalf) void k_tree_write_half(TArgs a) {
       for (uint32_t x = max(lo, sh); x < min(hi, tot); ++x) dst[x] = img[x];
     }
   }
-}
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
 }
 
 // n blobs of len bytes (len % 8 == 0) back to back: byte o of blob b =

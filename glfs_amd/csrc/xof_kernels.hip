@@ -27,14 +27,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_common.h"
 #include "kernels.h"
 
 namespace glfsx {
 namespace {
-
-constexpr uint32_t kIVx[8] = {0x6A09E667u, 0xBB67AE85u, 0x3C6EF372u, 0xA54FF53Au,
-                              0x510E527Fu, 0x9B05688Cu, 0x1F83D9ABu, 0x5BE0CD19u};
-enum : uint32_t { fStart = 1, fEnd = 2, fParent = 4, fRoot = 8 };
 
 __device__ __forceinline__ uint32_t rr(uint32_t x, uint32_t n) {
   return __builtin_amdgcn_alignbit(x, x, n);
@@ -55,7 +52,7 @@ __device__ __forceinline__ uint32_t rr(uint32_t x, uint32_t n) {
 __device__ void compress16(const uint32_t cv[8], const uint32_t m_in[16], uint64_t ctr,
                            uint32_t len, uint32_t flags, uint32_t out[16]) {
   uint32_t v[16] = {cv[0], cv[1], cv[2], cv[3], cv[4], cv[5], cv[6], cv[7],
-                    kIVx[0], kIVx[1], kIVx[2], kIVx[3],
+                    kIV[0], kIV[1], kIV[2], kIV[3],
                     uint32_t(ctr), uint32_t(ctr >> 32), len, flags};
   uint32_t m[16];
 #pragma unroll
@@ -125,7 +122,7 @@ __device__ void chunk_cv(const uint8_t *p, uint32_t n, uint64_t ctr, const uint3
     const uint32_t blen = b + 1 < nb ? 64u : n - 64 * b;
     uint32_t m[16];
     load_block(p + 64 * b, blen, m);
-    const uint32_t fl = base | (b == 0 ? fStart : 0u) | (b + 1 == nb ? fEnd : 0u);
+    const uint32_t fl = base | (b == 0 ? kChunkStart : 0u) | (b + 1 == nb ? kChunkEnd : 0u);
     if (b + 1 == nb && lb) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) lb->cv[i] = cv[i];
@@ -147,13 +144,14 @@ __device__ void parent_cv(const uint32_t l[8], const uint32_t r[8], const uint32
     m[8 + i] = r[i];
     cv[i] = key[i];
   }
-  compress8(cv, m, 0, 64, base | fParent);
+  compress8(cv, m, 0, 64, base | kParent);
 #pragma unroll
   for (int i = 0; i < 8; ++i) out[i] = cv[i];
 }
 
-// Pairwise left-complete merge of the k CVs in lds[0..8k) (tree_reduce in
-// post_kernels.hip); stops at 2 left when keep2 (the root's children).
+// Pairwise left-complete merge of the k CVs in lds[0..8k) (the tree of
+// tree_reduce_q in quad_kernels.h, with one lane per parent); stops at 2
+// left when keep2 (the root's children).
 __device__ void merge_cvs(uint32_t *lds, uint32_t k, uint32_t t, const uint32_t key[8],
                           uint32_t base, bool keep2) {
   while (k > (keep2 ? 2u : 1u)) {
@@ -229,7 +227,7 @@ __global__ __launch_bounds__(256) void k_b3_final(B3State *st, const uint8_t *sr
       for (int i = 0; i < 8; ++i) root_cv[i] = lb.cv[i];
       for (int i = 0; i < 16; ++i) root_m[i] = lb.m[i];
       root_len = lb.len;
-      root_flags = lb.flags | fRoot;
+      root_flags = lb.flags | kRoot;
     }
   }
   __syncthreads();
@@ -256,7 +254,7 @@ __global__ __launch_bounds__(256) void k_b3_final(B3State *st, const uint8_t *sr
         root_m[8 + i] = right[i];
       }
       root_len = 64;
-      root_flags = base | fParent | fRoot;
+      root_flags = base | kParent | kRoot;
     }
     __syncthreads();
   }

@@ -82,6 +82,46 @@ def test_library_reads_only_the_documented_knobs():
     assert calls == len(knobs)
 
 
+# The library's compile-time switches: GLFSX_PIPE=0 is built by build() and
+# run by tests/test_gpu_variants.py; the other three are diagnostic builds
+# (tools/build_variant.sh).  Alternates that no build compiles are deleted,
+# not kept behind a switch.
+BUILD_SWITCHES = {"GLFSX_PIPE", "GLFSX_WGTIME", "GLFSX_ONE_TIMING", "GLFSX_CONCAT_TRACE"}
+
+
+def test_library_has_only_the_kept_build_switches():
+    """Every GLFSX_* name in a preprocessor conditional or a #define of the
+    library's sources is one of the four kept switches."""
+    csrc = os.path.join(ROOT, "glfs_amd", "csrc")
+    names = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".cpp", ".hip", ".h")):
+            for line in open(os.path.join(csrc, f)):
+                if re.match(r"\s*#\s*(if|ifdef|ifndef|elif|define|undef)\b", line):
+                    names |= set(re.findall(r"\bGLFSX_\w+", line))
+    assert names == BUILD_SWITCHES, names ^ BUILD_SWITCHES
+
+
+def test_drivers_name_only_the_kept_build_switches():
+    """Every -DGLFSX_<NAME> in scripts/, tools/ and __graft_entry__.py names
+    a switch the sources still have."""
+    files = [os.path.join(ROOT, "__graft_entry__.py")]
+    for d in ("scripts", "tools"):
+        for base, _, fs in os.walk(os.path.join(ROOT, d)):
+            files += [os.path.join(base, f) for f in fs]
+    named = {}
+    for p in files:
+        try:
+            src = open(p, encoding="utf-8").read()
+        except UnicodeDecodeError:  # a built binary beside its source
+            continue
+        for n in re.findall(r"-D(GLFSX_\w+)", src):
+            named.setdefault(n, os.path.relpath(p, ROOT))
+    assert "GLFSX_PIPE" in named  # the search sees build()'s variant
+    stale = {n: p for n, p in named.items() if n not in BUILD_SWITCHES}
+    assert not stale, stale
+
+
 def test_file_route_only_for_plain_files(tmp_path):
     """Writer.read_from takes the parallel pread route only for a plain file
     (io.FileIO, or a buffered reader over one): a gzip / bz2 / lzma file

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build an A/B variant of the product library with extra -D flags:
-#   bash tools/build_variant.sh NAME "-DGLFSX_SCHED=1 ..."
+#   bash tools/build_variant.sh NAME "-DGLFSX_WGTIME=1 ..."
 # -> glfs_amd/libglfsx_NAME.so (load it with GLFSX_LIB=...; A/B runs only)
 set -e
 NAME=$1; DEFS=$2
