@@ -1,4 +1,5 @@
-// kernels.h -- internal interface between the host runtime (glfsx.cpp) and the
+// kernels.h -- internal interface between the host runtime (host.h and its
+// units: runtime, oneshot, copy_pool, writer, create, blobs, read) and the
 // gfx950 kernels: post_kernels.hip (the launches, with its fragments b3_arx.h,
 // pass_kernels.h, quad_kernels.h, one_kernels.h, small_kernels.h and
 // read_kernels.h holding the kernels by family), tree_kernels.hip and

@@ -65,6 +65,41 @@ def test_no_cpu_fallback_without_gpu():
         bigblob.Machine(1024).create(bigblob.MemStore(1024), None, b"abc")
 
 
+def test_device_entry_points_fail_cleanly_without_gpu():
+    """Entry points of every host unit reach the calling thread's state
+    (error text, device, fused mode) before any GPU call: without a GPU each
+    returns its error code and leaves a message, from any thread."""
+    import ctypes
+    import threading
+    from glfs_amd import _native as N
+    if N.device_count() > 0:
+        pytest.skip("GPU present")
+    got = []
+
+    def calls():
+        root, n = N.glfsx_root(), ctypes.c_uint64()
+        got.append([
+            N.lib.glfsx_set_device(0),
+            N.lib.glfsx_create_device(1 << 20, None, None, None, 0, None, ctypes.byref(root),
+                                      None, None),
+            N.lib.glfsx_root_from_level1(1024, None, None, bytes(128), 2, 17 * 1024,
+                                         ctypes.byref(root)),  # 17 blocks, 16 refs a node
+            N.lib.glfsx_post(bytes(32), b"x", 1, None, bytes(64), None),
+            N.lib.glfsx_decrypt_batch(b"x" * 64, 64, 64, bytes(64), bytes(64)),
+            N.lib.glfsx_tree_encode_device(1, None, bytes(16), bytes(4), None, bytes(16),
+                                           bytes(64), bytes(8), bytes(8), None, 0, None,
+                                           ctypes.byref(n), None),
+            N.lib.glfsx_clock_probe(1, None)])
+        assert "no HIP device" in N.last_error()
+
+    calls()
+    t = threading.Thread(target=calls)
+    t.start()
+    t.join()
+    assert len(got) == 2 and got[0] == got[1]
+    assert all(rc == N.GLFSX_E_DEVICE for rc in got[0]), got[0]
+
+
 def test_library_reads_only_the_documented_knobs():
     """the library reads five GLFSX_* variables, all
     tuning (tests/test_gpu_knobs.py runs each at a non-default value); every

@@ -1,8 +1,8 @@
 """One-shot posts (launch_one / k_one): a message of at most 64 KiB posted in
 one launch straight from pinned staging; up to 4 MiB in two launches over
 64 KiB spans (launch_med: k_med_dek / k_med_cid, last-arriving workgroup
-merges); concurrent callers coalesced into shared launches (glfsx.cpp
-one_post).  Every ref and ctext == the oracle's
+merges); concurrent callers coalesced into shared launches (oneshot.cpp
+one_post_many).  Every ref and ctext == the oracle's
 ref.go:98 post(); Writers whose tail blocks and index nodes take this route
 (block sizes <= 4 MiB) == the oracle Writer (blob.go:85-206), Post order
 included."""

@@ -289,6 +289,38 @@ def test_concat_from_store_memory_many_slabs(gpu, O):
     assert m.concat(ms, bs, None, *roots2).ref.marshal_binary() == want
 
 
+def test_more_live_writers_than_the_pools_keep(gpu, O):
+    """20 Writers open at once at 1 KiB blocks -- more than the 16 sets of
+    single-post staging the process-wide pool keeps, so freeing them destroys
+    the surplus -- then the same again in the same process (pooled resources
+    are reused and the pool overflows again), each round ending with a Concat
+    over five of the blobs (its pooled staging is taken, returned and taken
+    again).  Every root and every Writer's Post log (kind, ref, ctext) ==
+    the oracle's Create."""
+    from glfs_amd import bigblob
+    bs, n = 1024, 20
+    m = bigblob.Machine(bs)
+    datas = [O.fill_splitmix(3 * bs + 5, 500 + i) for i in range(n)]
+    wants = [O.create(d, bs, salt=None) for d in datas]
+    want_concat = O.create(b"".join(datas[:5]), bs, salt=None)[0]
+    for _ in range(2):
+        stores = [bigblob.MemStore(bs) for _ in range(n)]
+        writers = [m.new_writer(st, None) for st in stores]
+        for w, d in zip(writers, datas):
+            w.write(d)
+        roots = [w.finish() for w in writers]
+        for w in writers:
+            w.close()
+        for i, (root, st, (want_root, size, _, posts)) in enumerate(zip(roots, stores, wants)):
+            assert root.ref.marshal_binary() == want_root, i
+            assert (root.size, root.block_size) == (size, bs), i
+            got = [(k, r, st.blobs[r[:32]]) for k, r, _ in st.log]
+            assert got == [(k, r, ct) for k, r, _, ct in posts], i
+        ns = bigblob.NativeStore(bs, "trust")
+        parts = [m.create(ns, None, d) for d in datas[:5]]
+        assert m.concat(ns, bs, None, *parts).ref.marshal_binary() == want_concat
+
+
 class _ChunkyReader:
     """An io.Reader whose Reads return random amounts (1 B .. 3 MiB), read
     into the caller's buffer (readinto), like a pipe or socket."""
