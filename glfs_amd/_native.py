@@ -115,6 +115,7 @@ SIGNATURES = {
                                 _VP]),
     "glfsx_post_blobs_device": (_INT, [_U64, _CP, _CP, _VP, _VP, _VP, _U64, _U64, _VP,
                                        _VP, _VP]),
+    "glfsx_post_ragged_device": (_INT, [_CP, _CP, _VP, _VP, _VP, _U64, _U64, _VP, _VP, _VP]),
     "glfsx_chacha20_xor": (_INT, [_CP, _VP, _VP, _U64]),
     "glfsx_fill_splitmix_device": (_INT, [_VP, _U64, _U64, _U64, _VP]),
     "glfsx_decrypt_batch_device": (_INT, [_VP, _U64, _U64, _VP, _VP, _VP]),

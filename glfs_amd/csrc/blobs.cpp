@@ -34,15 +34,32 @@ int glfsx_post_blobs_device(uint64_t block_size, const uint8_t *salt,
   j.small_max = small_max;
   HIP_TRY(launch_post_small(j, s));
   if (max_len <= small_max) return 0;
-  // larger blobs (the caller said some may exceed 16 KiB): find them, then
-  // one post each (<= one block: the root is post(rawSalt, blob),
-  // blob.go:190-193) or a whole Create (several blocks)
+  // larger single-block blobs (the caller said some may exceed 16 KiB), up
+  // to 16 MiB: the ragged post, whatever their number and mix of lengths
+  // (the root is post(rawSalt, blob), blob.go:190-193)
+  const uint64_t rag_max = std::min(block_size, kMaxRaggedLen);
+  if (rag_max > small_max) {  // (not at block sizes of 16 KiB and less)
+    RaggedJob rj{};
+    rj.src = j.src;
+    rj.ctext = j.ctext;
+    rj.offs = d_offsets;
+    rj.lens = d_lengths;
+    rj.n = n;
+    rj.lo = small_max;
+    rj.hi = std::min(max_len, rag_max);
+    rj.refs = j.refs;
+    set_keys(rj, salts.raw, cid_key);
+    HIP_TRY(launch_post_ragged(rj, s));
+  }
+  if (max_len <= rag_max) return 0;
+  // what is left: find them, then a whole Create each (several blocks) or
+  // one post (a single block above 16 MiB)
   std::vector<uint64_t> offs(n), lens(n);
   HIP_TRY(hipMemcpyAsync(offs.data(), d_offsets, 8 * n, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(lens.data(), d_lengths, 8 * n, hipMemcpyDeviceToHost, s));
   HIP_TRY(stream_wait(s));
   for (uint64_t i = 0; i < n; ++i) {
-    if (lens[i] <= small_max) continue;
+    if (lens[i] <= rag_max) continue;  // posted above
     const uint8_t *src = static_cast<const uint8_t *>(d_data) + offs[i];
     uint8_t *ct = d_ctext ? static_cast<uint8_t *>(d_ctext) + offs[i] : nullptr;
     uint8_t *ref = static_cast<uint8_t *>(d_roots) + 64 * i;
@@ -59,6 +76,33 @@ int glfsx_post_blobs_device(uint64_t block_size, const uint8_t *salt,
       HIP_TRY(stream_wait(s));  // r lives on this frame
     }
   }
+  return 0;
+}
+
+int glfsx_post_ragged_device(const uint8_t salt[32], const uint8_t *cid_key,
+                             const void *d_data, const uint64_t *d_offsets,
+                             const uint64_t *d_lengths, uint64_t n, uint64_t max_len,
+                             void *d_ctext, void *d_refs, void *stream) {
+  if (n == 0) return 0;
+  if (!salt || !d_data || !d_offsets || !d_lengths || !d_refs)
+    return fail(GLFSX_E_ARG, "null argument");
+  if (max_len > kMaxRaggedLen)
+    return fail(GLFSX_E_UNSUPPORTED, "max_len %llu above the ragged post's %llu",
+                (unsigned long long)max_len, (unsigned long long)kMaxRaggedLen);
+  Ctx *c;
+  if (int e = ctx_get(&c)) return e;
+  hipStream_t s = pick_stream(c, stream);
+  RaggedJob rj{};
+  rj.src = static_cast<const uint8_t *>(d_data);
+  rj.ctext = static_cast<uint8_t *>(d_ctext);
+  rj.offs = d_offsets;
+  rj.lens = d_lengths;
+  rj.n = n;
+  rj.lo = kRaggedAll;
+  rj.hi = max_len;
+  rj.refs = static_cast<uint8_t *>(d_refs);
+  set_keys(rj, salt, cid_key);
+  HIP_TRY(launch_post_ragged(rj, s));
   return 0;
 }
 
@@ -87,29 +131,37 @@ int replay(const std::vector<CapturedPost> &posts, glfsx_post_fn post, void *pos
   return 0;
 }
 
-// glfsx_post_blobs' small blobs (<= small_max bytes), pipelined from host
-// memory: the blobs are taken in index order in groups whose bytes fit a
-// 64 MiB slot; each group's bytes are packed into pinned staging (runs of
-// blobs contiguous in `data` copied at once, by the copy pool), uploaded on
-// one stream, hashed one lane per blob (launch_post_small) on the context's
-// stream and their roots and ctext downloaded on a third, while the next
-// group is packed -- three slots in flight, so the host copy, both PCIe
-// directions and the kernels overlap.  A group's Posts are delivered when
-// its slot is reused or at the end, in blob order, the larger blobs' captured
-// Posts in their places: exactly n sequential PostBlob calls' order.
+// glfsx_post_blobs' single-block blobs of at most med_max bytes, pipelined
+// from host memory: the blobs are taken in index order in groups whose bytes
+// fit a 64 MiB slot; each group's bytes are packed into pinned staging (runs
+// of blobs contiguous in `data` copied at once, by the copy pool; a blob
+// above small_max starts on a 64-B boundary of the slot), uploaded on one
+// stream, hashed on the context's stream -- one lane per blob of at most
+// small_max bytes (launch_post_small), the longer ones by the ragged post
+// (launch_post_ragged) over the same slot -- and their roots and ctext
+// downloaded on a third, while the next group is packed -- three slots in
+// flight, so the host copy, both PCIe directions and the kernels overlap.  A
+// group's Posts are delivered when its slot is reused or at the end, in blob
+// order, the larger blobs' captured Posts in their places: exactly n
+// sequential PostBlob calls' order.
 constexpr uint64_t kGroupBytes = 64ull << 20;
 
-int complete_group(Ctx::BlobSlot &g, const uint64_t *lengths, uint64_t small_max,
+// Where a blob of len bytes goes in a slot filled up to o.
+inline uint64_t slot_offset(uint64_t o, uint64_t len, uint64_t small_max) {
+  return len > small_max ? (o + 63) & ~uint64_t(63) : o;
+}
+
+int complete_group(Ctx::BlobSlot &g, const uint64_t *lengths, uint64_t med_max,
                    const std::vector<std::vector<CapturedPost>> &big, glfsx_post_fn post,
                    void *post_ctx, uint8_t *roots_out) {
   if (!g.busy) return 0;
   HIP_TRY(hipEventSynchronize(g.done));
   g.busy = false;
   for (uint64_t i = g.i0; i < g.i1; ++i) {
-    if (lengths[i] <= small_max) {
+    if (lengths[i] <= med_max) {
       const uint8_t *ref = g.h_refs.u8() + 64 * (i - g.i0);
       memcpy(roots_out + 64 * i, ref, 64);
-      // a small blob's single Post: a data block, or the empty blob's
+      // a single-block blob's single Post: a data block, or the empty blob's
       // index node (blob.go:187-189)
       if (int e = deliver(post, post_ctx, lengths[i] ? 0 : 1, roots_out + 64 * i,
                           g.h_ct.u8() + g.loff[i - g.i0], lengths[i]))
@@ -123,7 +175,7 @@ int complete_group(Ctx::BlobSlot &g, const uint64_t *lengths, uint64_t small_max
 
 int post_small_groups(Ctx *c, uint64_t bs, const uint8_t *salt, const uint8_t *cid_key,
                       const uint8_t *data, const uint64_t *offsets, const uint64_t *lengths,
-                      uint64_t n, uint64_t small_max,
+                      uint64_t n, uint64_t small_max, uint64_t med_max,
                       const std::vector<std::vector<CapturedPost>> &big, glfsx_post_fn post,
                       void *post_ctx, uint8_t *roots_out) {
   Salts salts;
@@ -143,18 +195,20 @@ int post_small_groups(Ctx *c, uint64_t bs, const uint8_t *salt, const uint8_t *c
   while (i < n) {
     Ctx::BlobSlot &g = c->bslot[k];
     k = (k + 1) % 3;
-    if (int e = complete_group(g, lengths, small_max, big, post, post_ctx, roots_out)) {
+    if (int e = complete_group(g, lengths, med_max, big, post, post_ctx, roots_out)) {
       drain();
       return e;
     }
-    // the group: blobs [i, i1) whose small bytes fit kGroupBytes (a single
-    // blob always fits: small blobs are <= 16 KiB)
-    uint64_t i1 = i, bytes = 0, max_len = 0;
+    // the group: blobs [i, i1) whose packed bytes fit kGroupBytes (a single
+    // blob always fits: they are <= kMaxMedLen)
+    uint64_t i1 = i, bytes = 0, max_len = 0, max_med = 0;
     while (i1 < n) {
-      const uint64_t len = lengths[i1] <= small_max ? lengths[i1] : 0;
-      if (i1 > i && bytes + len > kGroupBytes) break;
-      bytes += len;
-      max_len = std::max(max_len, len);
+      const uint64_t len = lengths[i1] <= med_max ? lengths[i1] : 0;
+      const uint64_t end = slot_offset(bytes, len, small_max) + len;
+      if (i1 > i && end > kGroupBytes) break;
+      bytes = end;
+      if (len <= small_max) max_len = std::max(max_len, len);
+      else max_med = std::max(max_med, len);
       ++i1;
     }
     const uint64_t m = i1 - i;
@@ -174,11 +228,12 @@ int post_small_groups(Ctx *c, uint64_t bs, const uint8_t *salt, const uint8_t *c
       uint64_t o = 0, run_src = 0, run_dst = 0, run_len = 0;
       for (uint64_t j = 0; j < m; ++j) {
         const uint64_t idx = i + j, len = lengths[idx];
-        const bool small = len <= small_max;
-        lo[j] = small ? o : 0;
-        ll[j] = small ? len : kMaxSmallLen + 1;  // skipped by k_small
+        const bool here = len <= med_max;
+        if (here) o = slot_offset(o, len, small_max);
+        lo[j] = here ? o : 0;
+        ll[j] = here ? len : ~0ull;  // skipped by both posts
         g.loff[j] = lo[j];
-        if (!small || len == 0) continue;
+        if (!here || len == 0) continue;
         if (run_len && offsets[idx] == run_src + run_len && o == run_dst + run_len) {
           run_len += len;
         } else {
@@ -205,6 +260,19 @@ int post_small_groups(Ctx *c, uint64_t bs, const uint8_t *salt, const uint8_t *c
       j.refs = g.d_refs.u8();
       set_keys(j, salts, cid_key);
       HIP_TRY(launch_post_small(j, c->stream));
+      if (max_med) {  // blobs above small_max (k_small skipped them)
+        RaggedJob rj{};
+        rj.src = j.src;
+        rj.ctext = j.ctext;
+        rj.offs = j.offs;
+        rj.lens = j.lens;
+        rj.n = m;
+        rj.lo = small_max;
+        rj.hi = max_med;
+        rj.refs = j.refs;
+        set_keys(rj, salts.raw, cid_key);
+        HIP_TRY(launch_post_ragged(rj, c->stream));
+      }
       HIP_TRY(hipEventRecord(g.hashed, c->stream));
       HIP_TRY(hipStreamWaitEvent(c->s_down, g.hashed, 0));
       HIP_TRY(hipMemcpyAsync(g.h_refs.p, g.d_refs.p, 64 * m, hipMemcpyDeviceToHost, c->s_down));
@@ -225,7 +293,7 @@ int post_small_groups(Ctx *c, uint64_t bs, const uint8_t *salt, const uint8_t *c
   // the rest, oldest first
   for (int r = 0; r < 3; ++r) {
     Ctx::BlobSlot &g = c->bslot[(k + r) % 3];
-    if (int e = complete_group(g, lengths, small_max, big, post, post_ctx, roots_out)) {
+    if (int e = complete_group(g, lengths, med_max, big, post, post_ctx, roots_out)) {
       drain();
       return e;
     }
@@ -246,20 +314,17 @@ int glfsx_post_blobs(uint64_t block_size, uint64_t store_max, const uint8_t *sal
     return fail(GLFSX_E_BLOCKSIZE_GT_MAX, "blockSize %llu > maxSize %llu",
                 (unsigned long long)bs, (unsigned long long)store_max);
   if (int e = check_block_size(bs)) return e;
-  // small blobs go through the pipelined device batches (post_small_groups);
-  // single-block blobs of up to kMaxMedLen as one-shot posts, kMedBatchBytes
-  // at a time (their root is the block's ref, blob.go:190-193); larger ones
-  // Created one by one through the Writer.  The Posts of the latter two are
-  // captured and delivered in call order with the small blobs'.
-  std::vector<uint64_t> med;
+  // single-block blobs of up to kMaxMedLen go through the pipelined device
+  // batches (post_small_groups: their root is the block's ref,
+  // blob.go:190-193); larger ones are Created one by one through the Writer,
+  // their Posts captured and delivered in call order with the others'.
   std::vector<std::vector<CapturedPost>> big(n);
-  uint64_t n_small = 0;
+  uint64_t n_grouped = 0;
   const uint64_t small_max = small_max_for(bs);  // one block, <= 16 KiB
+  const uint64_t med_max = std::min(bs, kMaxMedLen);
   for (uint64_t i = 0; i < n; ++i) {
-    if (lengths[i] <= small_max) {
-      ++n_small;
-    } else if (lengths[i] <= bs && lengths[i] <= kMaxMedLen) {
-      med.push_back(i);
+    if (lengths[i] <= med_max) {
+      ++n_grouped;
     } else {
       glfsx_root r;
       if (int e = glfsx_create(bs, store_max, salt, cid_key,
@@ -269,54 +334,12 @@ int glfsx_post_blobs(uint64_t block_size, uint64_t store_max, const uint8_t *sal
       memcpy(roots_out + 64 * i, r.ref, 64);
     }
   }
-  Ctx *c;
-  if (int e = ctx_get(&c)) return e;
-  if (!med.empty()) {
-    Salts salts;
-    if (int e = derive_salts(c, salt, &salts)) return e;
-    for (size_t g0 = 0; g0 < med.size();) {
-      size_t g1 = g0;
-      uint64_t bytes = 0;
-      while (g1 < med.size() && (g1 == g0 || bytes + lengths[med[g1]] <= kMedBatchBytes)) {
-        bytes += (lengths[med[g1]] + 63) & ~uint64_t(63);
-        ++g1;
-      }
-      const size_t k = g1 - g0;
-      if (int e = c->h_bin.ensure(bytes)) return e;
-      if (post)
-        if (int e = c->h_bct.ensure(bytes)) return e;
-      if (int e = c->h_bref.ensure(64 * k)) return e;
-      std::vector<OneReq> reqs(k);
-      std::vector<OneReq *> rp(k);
-      uint64_t o = 0;
-      for (size_t j = 0; j < k; ++j) {
-        const uint64_t i = med[g0 + j], len = lengths[i];
-        par_memcpy(c->h_bin.u8() + o, static_cast<const uint8_t *>(data) + offsets[i], len);
-        OneDesc &d = reqs[j].d;
-        d.src = c->h_bin.dptr() + o;
-        d.ctext = post ? c->h_bct.dptr() + o : nullptr;
-        d.ref = c->h_bref.dptr() + 64 * j;
-        d.len = d.present = uint32_t(len);
-        set_keys(d, salts.raw, cid_key);
-        rp[j] = &reqs[j];
-        o += (len + 63) & ~uint64_t(63);
-      }
-      if (int e = one_post_many(c->dev, rp.data(), k)) return e;
-      for (size_t j = 0; j < k; ++j) {
-        const uint64_t i = med[g0 + j];
-        memcpy(roots_out + 64 * i, c->h_bref.u8() + 64 * j, 64);
-        if (post) {
-          const uint64_t off = reqs[j].d.ctext - c->h_bct.dptr();
-          capture_post(&big[i], 0, roots_out + 64 * i, c->h_bct.u8() + off, lengths[i]);
-        }
-      }
-      g0 = g1;
-    }
-  }
-  if (n_small) {
+  if (n_grouped) {
+    Ctx *c;
+    if (int e = ctx_get(&c)) return e;
     if (int e = post_small_groups(c, bs, salt, cid_key, static_cast<const uint8_t *>(data),
-                                  offsets, lengths, n, small_max, big, post, post_ctx,
-                                  roots_out))
+                                  offsets, lengths, n, small_max, med_max, big, post,
+                                  post_ctx, roots_out))
       return e;
   } else {
     for (uint64_t i = 0; i < n; ++i)

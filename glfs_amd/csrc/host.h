@@ -199,8 +199,7 @@ struct Ctx {
   DevBuf d_in, d_ct, d_refs, d_lvl_a, d_lvl_b, d_small, d_tree;
   PinBuf h_small, h_root;      // h_root: a root ref written by the kernels
   PinBuf h_oin, h_oct, h_oref;  // glfsx_post's one-shot staging
-  PinBuf h_bin, h_bct, h_bref;  // glfsx_post_blobs' one-shot staging
-  // glfsx_post_blobs' small blobs from host memory: groups of <= 64 MiB
+  // glfsx_post_blobs' single-block blobs from host memory: groups of <= 64 MiB
   // through three pinned slots, upload / hash / download on three streams
   struct BlobSlot {
     PinBuf h_in, h_ct, h_meta, h_refs;  // h_meta: local offsets then lengths

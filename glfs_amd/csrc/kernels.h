@@ -1,8 +1,9 @@
 // kernels.h -- internal interface between the host runtime (host.h and its
 // units: runtime, oneshot, copy_pool, writer, create, blobs, read) and the
 // gfx950 kernels: post_kernels.hip (the launches, with its fragments b3_arx.h,
-// pass_kernels.h, quad_kernels.h, one_kernels.h, small_kernels.h and
-// read_kernels.h holding the kernels by family), tree_kernels.hip and
+// pass_kernels.h, quad_kernels.h, one_kernels.h, small_kernels.h,
+// ragged_kernels.h and read_kernels.h holding the kernels by family),
+// tree_kernels.hip and
 // xof_kernels.hip (device_common.h: definitions the three share).  Not part
 // of the C-ABI.
 #pragma once
@@ -104,6 +105,29 @@ struct SmallJob {
 // The small route's limit for blobs of block size bs.
 inline uint64_t small_max_for(uint64_t bs) { return bs < kMaxSmallLen ? bs : kMaxSmallLen; }
 hipError_t launch_post_small(const SmallJob &job, hipStream_t s);
+
+// Many messages of unequal length in throughput form (ragged_kernels.h):
+// message i is src[offs[i] .. offs[i]+lens[i]); if lo < lens[i] <= hi its ref
+// (CID || DEK, the DEK keyed by salt as given) goes to refs + 64*i and its
+// ciphertext to ctext at the same offset; the other messages are skipped and
+// their ref slots left alone (lo = kRaggedAll: no lower bound, the empty
+// message included).  Work is handed out by BLAKE3 chunk, so it follows the
+// bytes, not n x the longest message; a fixed number of launches whatever n
+// (a plan of two, then at most three per pass) and one host wait, for the
+// plan's totals.  hi <= kMaxRaggedLen.
+constexpr uint64_t kMaxRaggedLen = 16ull << 20;
+constexpr uint64_t kRaggedAll = ~0ull;
+struct RaggedJob {
+  const uint8_t *src;
+  uint8_t *ctext;  // nullable; same offsets as src; may be src
+  const uint64_t *offs, *lens;  // device arrays
+  uint64_t n;
+  uint64_t lo, hi;
+  uint8_t *refs;
+  uint32_t salt[8], cid_key[8];
+  bool cid_keyed;
+};
+hipError_t launch_post_ragged(const RaggedJob &job, hipStream_t s);
 
 // One-shot posts (ref.go:98-161 for one message of at most kMaxOneLen bytes:
 // a glfs.PostBlob of a small blob, a Writer's tail block, an index node of a

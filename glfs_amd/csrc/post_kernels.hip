@@ -42,6 +42,7 @@ namespace {
 #include "quad_kernels.h"
 #include "one_kernels.h"
 #include "small_kernels.h"
+#include "ragged_kernels.h"
 #include "read_kernels.h"
 
 // The host side: launch plans and launches.
@@ -113,6 +114,12 @@ struct ScratchSlot {
   DcConst dcc_host;    // what was last copied there
   uint32_t *qctr;      // k_small_q: two banks of its item counter
   uint32_t qepoch;
+  uint8_t *rplan;      // ragged post: the plan's prefixes (RArgs::pre, wpre)
+  size_t rplan_bytes;
+  uint8_t *rcv;        // ragged post: chunk and group CVs (RArgs::cvs, gcv)
+  size_t rcv_bytes;
+  uint64_t *rtot;      // ragged post: the plan's three totals (pinned host)
+  uint64_t *d_rtot;    // the same words as the kernels address them
 };
 std::mutex g_scratch_mu;
 std::vector<ScratchSlot> g_scratch;
@@ -546,6 +553,9 @@ void release_stream_scratch(hipStream_t s) {
       if (g_scratch[i].err) (void)hipHostFree(g_scratch[i].err);
       if (g_scratch[i].dcc) (void)hipFree(g_scratch[i].dcc);
       if (g_scratch[i].qctr) (void)hipFree(g_scratch[i].qctr);
+      if (g_scratch[i].rplan) (void)hipFree(g_scratch[i].rplan);
+      if (g_scratch[i].rcv) (void)hipFree(g_scratch[i].rcv);
+      if (g_scratch[i].rtot) (void)hipHostFree(g_scratch[i].rtot);
     } else {
       continue;  // another device's stream of the same handle value
     }
@@ -753,6 +763,145 @@ hipError_t launch_post_small(const SmallJob &job, hipStream_t s) {
     if (e != hipSuccess) return e;
   }
   return launch_small_pass<true>(a, max_len, s);
+}
+
+// The ragged post's buffers on stream s: `plan` / `cv` bytes (0: leave that
+// one alone), grown when needed -- after the stream has drained -- and the
+// pinned words for the plan's totals.
+static hipError_t rag_get(hipStream_t s, size_t plan, size_t cv, uint8_t **d_plan,
+                          uint8_t **d_cv, uint64_t **tot, uint64_t **d_tot) {
+  StreamDevice sd(s);
+  if (sd.e != hipSuccess) return sd.e;
+  const int dev = sd.dev;
+  hipError_t e = hipSuccess;
+  std::lock_guard<std::mutex> lk(g_scratch_mu);
+  ScratchSlot *sl = nullptr;
+  for (ScratchSlot &x : g_scratch)
+    if (x.dev == dev && x.stream == s) sl = &x;
+  if (!sl) {
+    g_scratch.push_back(ScratchSlot{});
+    sl = &g_scratch.back();
+    sl->dev = dev;
+    sl->stream = s;
+  }
+  if (!sl->rtot) {
+    void *h = nullptr, *dp = nullptr;
+    e = hipHostMalloc(&h, 64, hipHostMallocCoherent);
+    if (e != hipSuccess) return e;
+    e = hipHostGetDevicePointer(&dp, h, 0);
+    if (e != hipSuccess) {
+      (void)hipHostFree(h);
+      return e;
+    }
+    sl->rtot = static_cast<uint64_t *>(h);
+    sl->d_rtot = static_cast<uint64_t *>(dp);
+  }
+  struct Grow {
+    uint8_t **p;
+    size_t *have, want;
+  } grow[2] = {{&sl->rplan, &sl->rplan_bytes, plan}, {&sl->rcv, &sl->rcv_bytes, cv}};
+  for (const Grow &g : grow) {
+    if (*g.have >= g.want) continue;
+    if (*g.p) {
+      e = hipStreamSynchronize(s);
+      if (e != hipSuccess) return e;
+      (void)hipFree(*g.p);
+    }
+    *g.p = nullptr;
+    *g.have = 0;
+    const size_t want = std::max(g.want + g.want / 4, size_t(1) << 20);
+    e = hipMalloc(reinterpret_cast<void **>(g.p), want);
+    if (e != hipSuccess) return e;
+    *g.have = want;
+  }
+  *d_plan = sl->rplan;
+  *d_cv = sl->rcv;
+  *tot = sl->rtot;
+  *d_tot = sl->d_rtot;
+  return hipSuccess;
+}
+
+template <bool CHACHA>
+static hipError_t launch_rag_chunk(const RArgs &a, hipStream_t s) {
+  const uint64_t tiles = (a.total + 255) >> 8;
+  const dim3 grid(uint32_t(std::min<uint64_t>(tiles, 1u << 20))), block(256);
+  // few tiles: the compiler's ARX form, as launch_g
+  if (tiles <= latency_wgs())
+    hipLaunchKernelGGL((k_rag_chunk<CHACHA, 0>), grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL((k_rag_chunk<CHACHA, 2>), grid, block, 0, s, a);
+  return hipGetLastError();
+}
+
+// One pass of the ragged post: the chunks, then the merge levels that have
+// work (tot: chunks, merge groups, messages of more than 256 chunks).
+template <bool CHACHA>
+static hipError_t launch_rag_pass(RArgs a, const uint64_t tot[3], hipStream_t s) {
+  a.total = tot[0];
+  hipError_t e = launch_rag_chunk<CHACHA>(a, s);
+  if (e != hipSuccess) return e;
+  if (tot[1]) {
+    a.total = tot[1];
+    hipLaunchKernelGGL(k_rag_merge_a, dim3(uint32_t(std::min<uint64_t>(tot[1], 1u << 20))),
+                       dim3(256), 0, s, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (tot[2]) {
+    a.total = tot[2];
+    hipLaunchKernelGGL(k_rag_merge_b, dim3(uint32_t(std::min<uint64_t>(tot[2], 1u << 20))),
+                       dim3(256), 0, s, a);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
+hipError_t launch_post_ragged(const RaggedJob &job, hipStream_t s) {
+  if (job.n == 0) return hipSuccess;
+  if (job.hi > kMaxRaggedLen) return hipErrorInvalidValue;
+  RArgs a{};
+  a.src = job.src;
+  a.ctext = job.ctext;
+  a.offs = job.offs;
+  a.lens = job.lens;
+  a.n = job.n;
+  a.lo = job.lo;
+  a.hi = job.hi;
+  a.refs = job.refs;
+  a.m = (job.n + kRagWG - 1) / kRagWG;
+  uint8_t *d_plan, *d_cv;
+  uint64_t *tot, *d_tot;
+  hipError_t e = rag_get(s, 8 * (job.n + 3 * (a.m + 1)), 0, &d_plan, &d_cv, &tot, &d_tot);
+  if (e != hipSuccess) return e;
+  a.pre = reinterpret_cast<uint64_t *>(d_plan);
+  a.wpre = a.pre + job.n;
+  hipLaunchKernelGGL(k_rag_count, dim3(uint32_t(a.m)), dim3(kRagWG), 0, s, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_rag_prefix<1024>, dim3(3), dim3(1024), 0, s, a.wpre, a.m, d_tot);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // the one host wait of the call: the totals size the CV scratch and the
+  // launches below
+  e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return e;
+  const uint64_t totals[3] = {__atomic_load_n(tot + 0, __ATOMIC_RELAXED),
+                              __atomic_load_n(tot + 1, __ATOMIC_RELAXED),
+                              __atomic_load_n(tot + 2, __ATOMIC_RELAXED)};
+  if (totals[0] == 0) return hipSuccess;  // nothing selected
+  e = rag_get(s, 0, 32 * (totals[0] + totals[1]), &d_plan, &d_cv, &tot, &d_tot);
+  if (e != hipSuccess) return e;
+  a.cvs = reinterpret_cast<uint32_t *>(d_cv);
+  a.gcv = a.cvs + 8 * totals[0];
+  for (int i = 0; i < 8; ++i) a.key[i] = job.salt[i];
+  a.base = kKeyed;
+  a.out_off = 32;
+  e = launch_rag_pass<false>(a, totals, s);
+  if (e != hipSuccess) return e;
+  for (int i = 0; i < 8; ++i) a.key[i] = job.cid_key[i];
+  a.base = job.cid_keyed ? kKeyed : 0u;
+  a.out_off = 0;
+  return launch_rag_pass<true>(a, totals, s);
 }
 
 #if GLFSX_ONE_TIMING

@@ -24,6 +24,9 @@
  *   glfsx_root_from_level1 GPUs; the caller gathers the level-1 refs
  *   glfsx_post_blobs*      glfs machine.go:64 PostBlob, batched over many
  *                          single-block blobs (tree.go:300-316 callers)
+ *   glfsx_post_ragged_device
+ *                          bigblob/ref.go:98-111   (*Machine).post, batched over
+ *                          messages of unequal length, minus the store.Post call
  *   glfsx_depth            bigblob/blob.go:256-264 depth()
  *   glfsx_tree_encode      tree.go:300-316 TreeWriter.Put's JSON lines, batched
  *   glfsx_store_*          the store under ref.go:103 (bcsdk.WO / MemStore [ext])
@@ -345,8 +348,10 @@ int glfsx_root_from_level1(uint64_t block_size, const uint8_t *salt,
  * has root post(rawSalt, blob) (blob.go:190-193), the empty blob
  * post(indexSalt, "") (blob.go:187-189); rawSalt / indexSalt derive from
  * `salt` (glfs: the type salt, machine.go:50-54).  Blobs of <= 16 KiB are
- * hashed one lane each in one launch pair; larger ones (any size, several
- * blocks included) go through the Writer.  Writes the 64-byte root ref
+ * hashed one lane each in one launch pair, larger single-block blobs of up
+ * to 4 MiB by the ragged post (glfsx_post_ragged_device's kernels) in the
+ * same pipelined groups; the others (several blocks, or above 4 MiB) go
+ * through the Writer.  Writes the 64-byte root ref
  * (CID||DEK) per blob; `post` is called for every Post of blob 0, then blob
  * 1, ... exactly as n sequential PostBlob calls would. */
 int glfsx_post_blobs(uint64_t block_size, uint64_t store_max, const uint8_t *salt,
@@ -354,14 +359,29 @@ int glfsx_post_blobs(uint64_t block_size, uint64_t store_max, const uint8_t *sal
                      const uint64_t *offsets, const uint64_t *lengths, uint64_t n,
                      glfsx_post_fn post, void *post_ctx, uint8_t *roots_out);
 /* Device-resident: d_offsets / d_lengths are device arrays; max_len is the
- * largest length (caller-known; when it exceeds 16 KiB the lengths are read
- * back and the larger blobs posted one by one, synchronising the stream).
- * Enqueued on stream. */
+ * largest length (caller-known).  Single-block blobs above 16 KiB and of at
+ * most 16 MiB take the ragged post below: a fixed number of launches and one
+ * wait for its plan.  Only when max_len exceeds min(block_size, 16 MiB) are
+ * the lengths read back and the remaining blobs (several blocks, or above
+ * 16 MiB) posted one by one, synchronising the stream.  Enqueued on stream. */
 int glfsx_post_blobs_device(uint64_t block_size, const uint8_t *salt,
                             const uint8_t *cid_key, const void *d_data,
                             const uint64_t *d_offsets, const uint64_t *d_lengths,
                             uint64_t n, uint64_t max_len, void *d_ctext,
                             void *d_roots, void *stream);
+
+/* ref.go:98-111 post, batched over n messages of unequal length (message i =
+ * d_data[d_offsets[i] .. +d_lengths[i]), 0 <= length <= 16 MiB): ref i
+ * (CID || DEK) to d_refs + 64 i, ciphertext (nullable; may be d_data) at the
+ * same offsets.  `salt` keys every DEK as given (no raw/index derivation, no
+ * empty-blob rule: those are glfsx_post_blobs_device's).  max_len bounds the
+ * lengths.  Device pointers; enqueued on stream; a fixed number of launches
+ * whatever n. */
+int glfsx_post_ragged_device(const uint8_t salt[32], const uint8_t *cid_key,
+                             const void *d_data, const uint64_t *d_offsets,
+                             const uint64_t *d_lengths, uint64_t n,
+                             uint64_t max_len, void *d_ctext, void *d_refs,
+                             void *stream);
 
 /* --- tree blobs (tree.go:284-320; BASELINE config 4) -------------------- */
 /* TreeWriter.Put's json.Encoder.Encode(TreeEntry) (tree.go:300-316) for n
