@@ -23,6 +23,9 @@ GLFSX_E_ARG = -5
 GLFSX_E_UNSUPPORTED = -6
 GLFSX_E_NOMEM = -7
 GLFSX_E_IO = -8
+GLFSX_E_CORRUPT = -9
+GLFSX_BAD_CID = 1
+GLFSX_BAD_DEK = 2
 GLFSX_STORE_TRUST = 0
 GLFSX_STORE_HASH = 1
 
@@ -120,6 +123,10 @@ SIGNATURES = {
     "glfsx_fill_splitmix_device": (_INT, [_VP, _U64, _U64, _U64, _VP]),
     "glfsx_decrypt_batch_device": (_INT, [_VP, _U64, _U64, _VP, _VP, _VP]),
     "glfsx_decrypt_batch": (_INT, [_VP, _U64, _U64, _VP, _VP]),
+    "glfsx_open_batch_device": (_INT, [_CP, _CP, _VP, _U64, _U64, _VP, _VP, _VP, _VP]),
+    "glfsx_open_batch": (_INT, [_CP, _CP, _VP, _U64, _U64, _VP, _VP, _VP,
+                                ctypes.POINTER(ctypes.c_uint64)]),
+    "glfsx_set_open_route": (_INT, [_INT]),
     "glfsx_sink_count": (_INT, [_VP, _INT, _VP, _VP, _U64]),
     "glfsx_tree_encode": (_INT, [_U64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U64,
                                  ctypes.POINTER(ctypes.c_uint64), _VP]),
@@ -199,6 +206,13 @@ def set_latency_wgs(wgs: int) -> int:
     """Tuning knob (include/glfsx.h): launches of at most `wgs` workgroups
     use the latency-mode kernels.  Returns the previous value."""
     return lib.glfsx_set_latency_wgs(wgs)
+
+
+def set_open_route(route: int) -> int:
+    """Test hook (include/glfsx.h): the verified read's route -- 0 auto, 1 the
+    composed passes, 2 the one-pass kernel wherever able.  Returns the
+    previous value."""
+    return lib.glfsx_set_open_route(route)
 
 
 def set_split_target(wgs: int) -> int:

@@ -18,7 +18,7 @@ from dataclasses import dataclass
 from typing import BinaryIO, Optional, Protocol, Union
 
 from . import _native as N
-from ._native import Panic, StoreError  # noqa: F401  (re-exported)
+from ._native import GlfsxError, Panic, StoreError  # noqa: F401  (re-exported)
 
 DEK_SIZE = 32          # ref.go:16
 CID_SIZE = 32          # blobcache.CIDSize [ext]
@@ -416,28 +416,88 @@ class Machine:
                 self._traverse(store, bs, level - 1, r2, enter, exit)
         exit(level, x)
 
-    def sync(self, dst, src, x: Root, fn=None) -> None:
+    def sync(self, dst, src, x: Root, fn=None, verify: bool = False,
+             cid_key: Optional[bytes] = None) -> None:
         """blob.go:270-315 Sync: nothing to do if dst has the root CID;
         otherwise call fn(reader), then copy every reachable blob, children
         before their index node (the reference's post-order).  The index
-        levels are read one batched GPU decrypt per level."""
+        levels are read one batched GPU decrypt per level.
+
+        verify: the reference's copyBlob ends in dst.Post, which re-hashes the
+        bytes (blob.go:307-315); a pre-hashed dst does not.  With verify every
+        blob's CID (keyed by cid_key) is checked on the GPU before it is
+        handed to dst -- index nodes in the level walk, data blocks in
+        batches of at most 64 MiB, CID only, no plaintext -- and the bytes
+        posted are the bytes checked.  A mismatch raises ErrCorrupt and
+        nothing more is posted; the post order is unchanged."""
         if exists_unit(dst, x.ref.cid):
             return
         if fn is not None:
             fn(self.new_reader(src, x))
-        levels = _tree_levels(src.get, x)
+        nodes: dict = {}   # cid -> checked ctext of the index nodes
+        batch: dict = {}   # the same for the data blocks of the current batch
+        if verify:
+            levels = _tree_levels(src.get, x, None, cid_key, _check=True, _keep=nodes)
+        else:
+            levels = _tree_levels(src.get, x)
         bf = branching_factor(x.block_size)
+        data = levels[-1]
+        per = max(1, SYNC_VERIFY_BYTES // max(x.block_size, 1))
+
+        def copy(ref: Ref, k: int, j: int) -> None:
+            if not verify:
+                return copy_blob(dst, src, ref)
+            if k + 1 < len(levels):
+                ct = nodes[ref.cid]
+            else:
+                if ref.cid not in batch:   # the next batch: check it first
+                    part = data[j:j + per]
+                    cts = [src.get(r.cid) for r in part]
+                    try:
+                        open_level(cts, part, x.block_size, None, cid_key, want_ptext=False)
+                    except ErrCorrupt as e:
+                        raise ErrCorrupt(j + e.index, e.cid, e.status, 0) from None
+                    batch.clear()
+                    batch.update((r.cid, c) for r, c in zip(part, cts))
+                ct = batch[ref.cid]
+            dst.post(ct, ref.cid + bytes(DEK_SIZE), KIND_COPY)
 
         def emit(k: int, j: int) -> None:
             if k + 1 < len(levels):
                 for c in range(j * bf, min((j + 1) * bf, len(levels[k + 1]))):
                     emit(k + 1, c)
-            copy_blob(dst, src, levels[k][j])
+            copy(levels[k][j], k, j)
 
         if x.size == 0:
+            if verify:
+                _check_empty(x.ref, None, cid_key, src.get(x.ref.cid))
             copy_blob(dst, src, x.ref)
         else:
             emit(0, 0)
+
+    def verify(self, store, root: Root, salt: Optional[bytes] = None,
+               cid_key: Optional[bytes] = None) -> int:
+        """fsck of root's tree: every reachable blob's bytes must hash to the
+        CID they are stored under (keyed by cid_key), and -- when the salt
+        the blob was created with is given -- every blob's plaintext to its
+        ref's DEK.  One batched GPU call per index level, the data level in
+        batches of at most 64 MiB without plaintext.  Returns the number of
+        blobs checked; raises ErrCorrupt (with the blob's CID and level)."""
+        if root.size == 0:
+            _check_empty(root.ref, salt, cid_key, store.get(root.ref.cid))
+            return 1
+        levels = _tree_levels(store.get, root, salt, cid_key, _check=True)
+        raw = derive_key(salt, b"raw") if salt is not None else None
+        data, bs = levels[-1], root.block_size
+        per = max(1, SYNC_VERIFY_BYTES // bs)
+        for j in range(0, len(data), per):
+            part = data[j:j + per]
+            try:
+                open_level([store.get(r.cid) for r in part], part, bs, raw, cid_key,
+                           want_ptext=False)
+            except ErrCorrupt as e:
+                raise ErrCorrupt(j + e.index, e.cid, e.status, 0) from None
+        return sum(len(lv) for lv in levels)
 
     def populate(self, store, root: Root, dst) -> None:
         """blob.go:317-331 Populate: add every reachable CID that dst lacks
@@ -607,6 +667,25 @@ class ErrNotFound(KeyError):
         self.cid = cid
 
 
+class ErrCorrupt(GlfsxError):
+    """A blob failed the verified read (glfsx_open_batch): its bytes do not
+    hash to the CID it was fetched under (status & 1), or its plaintext is
+    not the one its ref's DEK was derived from (status & 2).  index: the
+    blob's position in the batch or level it was checked in; level: its tree
+    level (0 = data blocks) when known."""
+
+    def __init__(self, index: int, cid: bytes, status: int, level: Optional[int] = None):
+        what = {1: "CID", 2: "DEK", 3: "CID and DEK"}.get(status, f"status {status}")
+        where = "" if level is None else f" at level {level}"
+        super().__init__(N.GLFSX_E_CORRUPT,
+                         f"blob {bytes(cid).hex()} (index {index}{where}) failed its "
+                         f"{what} check")
+        self.index, self.cid, self.status, self.level = index, bytes(cid), status, level
+
+    def at_level(self, level: int) -> "ErrCorrupt":
+        return ErrCorrupt(self.index, self.cid, self.status, level)
+
+
 class NativeStore:
     """The native store of the C-ABI (glfsx_store_*, include/glfsx.h): an
     in-memory content-addressed store whose Post takes the GPU-computed CID
@@ -749,18 +828,117 @@ def decrypt_level(ctexts, refs, block_size: int) -> list:
     return [raw[i * block_size:i * block_size + len(c)] for i, c in enumerate(ctexts)]
 
 
-def _tree_levels(get, root: Root) -> list:
+SYNC_VERIFY_BYTES = 64 << 20   # data blocks checked per batch (sync, verify)
+
+
+def _open_call(salt, cid_key, data, total: int, block_size: int, rb: bytes, out):
+    """One glfsx_open_batch call; returns None, or (index, status) of the
+    first bad block."""
+    n = -(-total // block_size)
+    st = (ctypes.c_uint32 * n)()
+    rc = N.lib.glfsx_open_batch(_salt_arg(salt), cid_key, data, total, block_size, rb, out,
+                                st, None)
+    if rc == N.GLFSX_E_CORRUPT:
+        i = next(i for i in range(n) if st[i])
+        return i, st[i]
+    N.check(rc)
+    return None
+
+
+def _empty_status(ref: Ref, level_salt: Optional[bytes], cid_key: Optional[bytes]) -> int:
+    """The status word of a blob of no bytes (nothing to hash on the device):
+    its ref must be what posting b"" under the level's salt gives."""
+    got = ctypes.create_string_buffer(REF_SIZE)
+    N.check(N.lib.glfsx_post(_salt_arg(level_salt) or bytes(32), b"", 0,
+                             ctypes.create_string_buffer(1), got, cid_key))
+    return (N.GLFSX_BAD_CID if got.raw[:CID_SIZE] != ref.cid else 0) | \
+        (N.GLFSX_BAD_DEK if level_salt is not None and got.raw[CID_SIZE:] != ref.dek else 0)
+
+
+def _check_empty(ref: Ref, salt: Optional[bytes], cid_key: Optional[bytes],
+                 stored: Optional[bytes] = None) -> None:
+    """The empty blob (blob.go:120-206: one post of no bytes under the index
+    salt of the blob's salt); stored: what the store holds under its CID."""
+    status = _empty_status(ref, derive_key(salt, b"index") if salt is not None else None,
+                           cid_key)
+    if stored:   # bytes under the CID of no bytes
+        status |= N.GLFSX_BAD_CID
+    if status:
+        raise ErrCorrupt(0, ref.cid, status, 0)
+
+
+def open_level(ctexts, refs, block_size: int, salt: Optional[bytes],
+               cid_key: Optional[bytes] = None, want_ptext: bool = True) -> list:
+    """decrypt_level with the checks: every ctext must hash to its ref's CID
+    (keyed by cid_key) and, when salt is given (the level's salt as post took
+    it: rawSalt or indexSalt), its plaintext to its ref's DEK -- one
+    glfsx_open_batch call for a uniform level, one call per blob otherwise.
+    Returns the plaintexts in order (an empty list when want_ptext is
+    false); raises ErrCorrupt for the first bad blob."""
+    n = len(ctexts)
+    if n == 0:
+        return []
+    uniform = not (any(len(c) != block_size for c in ctexts[:-1])
+                   or len(ctexts[-1]) > block_size or len(ctexts[-1]) == 0 or block_size % 64)
+    outs = []
+    if uniform:
+        data = b"".join(ctexts)
+        rb = b"".join(r.marshal_binary() for r in refs)
+        out = ctypes.create_string_buffer(len(data)) if want_ptext else None
+        bad = _open_call(salt, cid_key, data, len(data), block_size, rb, out)
+        if bad:
+            raise ErrCorrupt(bad[0], refs[bad[0]].cid, bad[1])
+        if want_ptext:
+            raw = out.raw
+            outs = [raw[i * block_size:i * block_size + len(c)] for i, c in enumerate(ctexts)]
+        return outs
+    for i, (r, c) in enumerate(zip(refs, ctexts)):
+        c = bytes(c)
+        if len(c) == 0:
+            status = _empty_status(r, salt, cid_key)
+            if status:
+                raise ErrCorrupt(i, r.cid, status)
+            outs.append(b"")
+            continue
+        out = ctypes.create_string_buffer(len(c)) if want_ptext else None
+        bad = _open_call(salt, cid_key, c, len(c), -(-len(c) // 64) * 64, r.marshal_binary(), out)
+        if bad:
+            raise ErrCorrupt(i, r.cid, bad[1])
+        if want_ptext:
+            outs.append(out.raw)
+    return outs if want_ptext else []
+
+
+def _tree_levels(get, root: Root, salt: Optional[bytes] = None,
+                 cid_key: Optional[bytes] = None, *, _check: bool = False,
+                 _keep: Optional[dict] = None) -> list:
     """The refs of every level of root's tree, top (the root) first, data
     blocks last: each index level is fetched with get(cid) and decrypted in
-    one batch (blob.go:53-69 getPiece's walk, level by level)."""
+    one batch (blob.go:53-69 getPiece's walk, level by level).  With a salt
+    (the blob's, as Create took it) or a cid_key the index nodes go through
+    open_level -- CID checked, and DEK under DeriveKey(salt, "index") when
+    the salt is given -- and a bad node raises ErrCorrupt with its level;
+    with neither, nothing is checked.  (_check: check CIDs even with neither;
+    _keep: a dict that receives cid -> ctext of every index node.)"""
     bs = root.block_size
     bf = branching_factor(bs)
     lvl = depth(root.size, bs)
     n0 = -(-root.size // bs)
     levels = [[root.ref]]
+    checked = _check or salt is not None or cid_key is not None
+    index_salt = derive_key(salt, b"index") if salt is not None and lvl > 0 else None
     for k in range(lvl, 0, -1):
         refs = levels[-1]
-        nodes = decrypt_level([get(r.cid) for r in refs], refs, bs)
+        cts = [get(r.cid) for r in refs]
+        if checked:
+            try:
+                nodes = open_level(cts, refs, bs, index_salt, cid_key)
+            except ErrCorrupt as e:
+                raise e.at_level(k) from None
+        else:
+            nodes = decrypt_level(cts, refs, bs)
+        if _keep is not None:
+            _keep.update((r.cid, c) for r, c in zip(refs, cts))
         want = -(-n0 // bf ** (k - 1))          # refs at level k-1
         child = []
         for node in nodes:
@@ -772,20 +950,39 @@ def _tree_levels(get, root: Root) -> list:
     return levels
 
 
-def read_all(store, root: Root) -> bytes:
+def read_all(store, root: Root, salt: Optional[bytes] = None,
+             cid_key: Optional[bytes] = None) -> bytes:
     """Read side (blob.go:31-69 ReadAt/getPiece, ref.go:113-126 getF) of a
     whole blob: the index levels and then all data blocks, each level one
-    batched GPU decrypt (the data level straight into the output buffer)."""
+    batched GPU decrypt (the data level straight into the output buffer).
+    With the blob's salt (or the store's cid_key) every blob on the way is
+    checked as it is decrypted (index levels: open_level; the data level:
+    glfsx_open_batch under DeriveKey(salt, "raw")) and corrupt bytes raise
+    ErrCorrupt instead of being returned; with neither, nothing is checked."""
+    checked = salt is not None or cid_key is not None
     if root.size == 0:
+        if checked:
+            _check_empty(root.ref, salt, cid_key)
         return b""
     bs = root.block_size
-    data_refs = _tree_levels(store.get, root)[-1]
+    data_refs = _tree_levels(store.get, root, salt, cid_key)[-1]
+    raw = derive_key(salt, b"raw") if salt is not None else None
     if bs % 64:
+        if checked:
+            return b"".join(open_level([store.get(r.cid) for r in data_refs], data_refs, bs,
+                                       raw, cid_key))
         return b"".join(crypto_xor(r.dek, store.get(r.cid)) for r in data_refs)
     ct = _gather(store, data_refs, root.size)
     out = bytearray(root.size)
     rb = b"".join(r.marshal_binary() for r in data_refs)
     obuf = (ctypes.c_char * len(out)).from_buffer(out)
-    N.check(N.lib.glfsx_decrypt_batch(ct.ctypes.data, len(ct), bs, rb, obuf))
-    del obuf
+    try:
+        if checked:
+            bad = _open_call(raw, cid_key, ct.ctypes.data, len(ct), bs, rb, obuf)
+            if bad:
+                raise ErrCorrupt(bad[0], data_refs[bad[0]].cid, bad[1], 0)
+        else:
+            N.check(N.lib.glfsx_decrypt_batch(ct.ctypes.data, len(ct), bs, rb, obuf))
+    finally:
+        del obuf
     return bytes(out)

@@ -2,7 +2,8 @@
 // units: runtime, oneshot, copy_pool, writer, create, blobs, read) and the
 // gfx950 kernels: post_kernels.hip (the launches, with its fragments b3_arx.h,
 // pass_kernels.h, quad_kernels.h, one_kernels.h, small_kernels.h,
-// ragged_kernels.h and read_kernels.h holding the kernels by family),
+// ragged_kernels.h, read_kernels.h and open_kernels.h holding the kernels by
+// family),
 // tree_kernels.hip and
 // xof_kernels.hip (device_common.h: definitions the three share).  Not part
 // of the C-ABI.
@@ -174,6 +175,30 @@ hipError_t launch_med_v(const OneDesc &d, hipStream_t s);
 hipError_t launch_decrypt(const uint8_t *ctext, uint8_t *ptext, uint64_t n,
                           uint64_t bs, uint64_t last_len, const uint8_t *refs,
                           hipStream_t s);
+
+// Read side with the checks (open_kernels.h): block j of n contiguous blocks
+// (bs % 64 == 0, bs <= kMaxMsgLen; the last one last_len bytes) is checked
+// against refs[j] -- its ctext must hash to the CID and, when salted, its
+// plaintext (ChaCha20 with the ref's DEK) to the DEK under `salt` as given --
+// and decrypted to ptext when that is set.  status[j] (every j < n, no
+// pre-zeroing) = 1 (CID mismatch) | 2 (DEK mismatch), 0 when both match; the
+// plaintext is written either way.  Two routes with the same results: k_open
+// (one pass, one workgroup per block: salted, bs <= 2 MiB) and the composed
+// one (CID pass, launch_decrypt, DEK pass, k_open_compare) for everything
+// else; set_open_route picks (0 auto, 1 composed, 2 fused wherever able;
+// other values change nothing) and returns the previous value.
+struct OpenJob {
+  const uint8_t *ctext;
+  uint8_t *ptext;               // nullable; may equal ctext
+  uint64_t n, bs, last_len;
+  const uint8_t *refs;          // dense, 64 B per block, 4-B aligned
+  uint32_t *status;             // 4-B aligned
+  uint32_t salt[8];
+  uint32_t cid_key[8];          // the IV when unkeyed
+  bool salted, cid_keyed;
+};
+hipError_t launch_open(const OpenJob &, hipStream_t);
+int set_open_route(int route);
 
 // Synthetic splitmix64 byte stream (see oracle_fill_splitmix); offset % 8 == 0.
 hipError_t launch_fill(uint8_t *dst, uint64_t offset, uint64_t n, uint64_t seed,

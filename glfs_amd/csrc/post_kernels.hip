@@ -44,6 +44,7 @@ namespace {
 #include "small_kernels.h"
 #include "ragged_kernels.h"
 #include "read_kernels.h"
+#include "open_kernels.h"
 
 // The host side: launch plans and launches.
 
@@ -120,6 +121,8 @@ struct ScratchSlot {
   size_t rcv_bytes;
   uint64_t *rtot;      // ragged post: the plan's three totals (pinned host)
   uint64_t *d_rtot;    // the same words as the kernels address them
+  uint8_t *open;       // verified read, composed route: digests, plaintext
+  size_t open_bytes;
 };
 std::mutex g_scratch_mu;
 std::vector<ScratchSlot> g_scratch;
@@ -556,6 +559,7 @@ void release_stream_scratch(hipStream_t s) {
       if (g_scratch[i].rplan) (void)hipFree(g_scratch[i].rplan);
       if (g_scratch[i].rcv) (void)hipFree(g_scratch[i].rcv);
       if (g_scratch[i].rtot) (void)hipHostFree(g_scratch[i].rtot);
+      if (g_scratch[i].open) (void)hipFree(g_scratch[i].open);
     } else {
       continue;  // another device's stream of the same handle value
     }
@@ -1041,6 +1045,141 @@ hipError_t launch_chacha_xor(const uint32_t k[8], const uint8_t *src,
   if (grid > 65536) grid = 65536;
   hipLaunchKernelGGL(k_chacha_xor, dim3(uint32_t(grid)), dim3(256), 0, s, a);
   return hipGetLastError();
+}
+
+// ---- The verified read (open_kernels.h) ----
+
+// Route of launch_open: 0 auto, 1 always composed, 2 fused wherever k_open
+// is able (glfsx_set_open_route: tests and measurements of both).
+static std::atomic<int> g_open_route{0};
+int set_open_route(int route) {
+  if (route < 0 || route > 2) return g_open_route.load(std::memory_order_relaxed);
+  return g_open_route.exchange(route, std::memory_order_relaxed);
+}
+
+// Where auto takes the fused route: only at shapes whose neighbours in the
+// sweep of scripts/open_rate.py had k_open's median at or above the composed
+// route's in the same run (profiles/open/open_rate.json, DESIGN.md "k_open --
+// the verified read").  From 1024 blocks on (one workgroup per block then
+// fills every CU's four slots; at 512 the two routes tie and at 256 the
+// composed one wins by a fifth), blocks of at least 256 KiB (at 64 KiB only
+// one wave of a workgroup has chunks: 0.84 of composed), and 1 GiB in all
+// (the smallest total measured at each block size).
+constexpr uint64_t kOpenFusedMinBlocks = 1024;
+constexpr uint64_t kOpenFusedMinBs = 256ull << 10;
+constexpr uint64_t kOpenFusedMinBytes = 1ull << 30;
+constexpr uint64_t kOpenFusedMaxBs = 2ull << 20;  // 256 lanes x 8 chunks
+
+// The composed route's scratch on stream s: `bytes`, grown when needed after
+// the stream has drained.
+static hipError_t open_get(hipStream_t s, size_t bytes, uint8_t **p) {
+  StreamDevice sd(s);
+  if (sd.e != hipSuccess) return sd.e;
+  std::lock_guard<std::mutex> lk(g_scratch_mu);
+  ScratchSlot *sl = nullptr;
+  for (ScratchSlot &x : g_scratch)
+    if (x.dev == sd.dev && x.stream == s) sl = &x;
+  if (!sl) {
+    g_scratch.push_back(ScratchSlot{});
+    sl = &g_scratch.back();
+    sl->dev = sd.dev;
+    sl->stream = s;
+  }
+  if (sl->open_bytes < bytes) {
+    if (sl->open) {
+      hipError_t e = hipStreamSynchronize(s);
+      if (e != hipSuccess) return e;
+      (void)hipFree(sl->open);
+    }
+    sl->open = nullptr;
+    sl->open_bytes = 0;
+    const size_t want = std::max(bytes + bytes / 4, size_t(1) << 20);
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&sl->open), want);
+    if (e != hipSuccess) return e;
+    sl->open_bytes = want;
+  }
+  *p = sl->open;
+  return hipSuccess;
+}
+
+template <int G>
+static hipError_t launch_open_g(const OArgs &a, bool aligned, hipStream_t s) {
+  const dim3 grid(uint32_t(a.n)), block(256);
+  if (aligned)
+    hipLaunchKernelGGL((k_open<G, true, 2>), grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL((k_open<G, false, 2>), grid, block, 0, s, a);
+  return hipGetLastError();
+}
+
+// Existing launches plus k_open_compare: the CID of the ctext and, when
+// salted, the DEK of the decrypted plaintext go to a 64-B slot per block,
+// which the last kernel compares with the refs.
+static hipError_t launch_open_composed(const OpenJob &job, hipStream_t s) {
+  const uint64_t total = (job.n - 1) * job.bs + job.last_len;
+  const bool own_pt = !job.ptext && job.salted;
+  const size_t dig = size_t(job.n) * 64;
+  uint8_t *scr;
+  hipError_t e = open_get(s, dig + (own_pt ? size_t(total) + 64 : 0), &scr);
+  if (e != hipSuccess) return e;
+  uint8_t *pt = own_pt ? scr + dig : job.ptext;
+  const uint64_t maxlen = job.n > 1 ? job.bs : job.last_len;
+  PostJob pj{};
+  pj.src = job.ctext;
+  pj.stride = pj.msg_len = job.bs;
+  pj.last_len = job.last_len;
+  pj.n = job.n;
+  pj.out = RefLayout{scr, ~0ull, 0};
+  KArgs a = make_args(pj);
+  for (int i = 0; i < 8; ++i) a.key[i] = job.cid_key[i];
+  a.base = job.cid_keyed ? kKeyed : 0u;
+  a.out_off = 0;
+  e = launch_pass<false>(a, maxlen, is_aligned(pj), s);
+  if (e != hipSuccess) return e;
+  if (pt) {
+    e = launch_decrypt(job.ctext, pt, job.n, job.bs, job.last_len, job.refs, s);
+    if (e != hipSuccess) return e;
+  }
+  if (job.salted) {
+    pj.src = pt;
+    for (int i = 0; i < 8; ++i) pj.salt[i] = job.salt[i];
+    e = launch_keyed_hash(pj, 32, s);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_open_compare, dim3(uint32_t((job.n + 255) / 256)), dim3(256), 0, s,
+                     scr, job.refs, job.status, job.n, job.salted ? 1u : 0u);
+  return hipGetLastError();
+}
+
+hipError_t launch_open(const OpenJob &job, hipStream_t s) {
+  if (job.n == 0) return hipSuccess;
+  if (job.bs % 64 || job.bs > kMaxMsgLen || job.last_len > job.bs || job.n > 0x7fffffffull)
+    return hipErrorInvalidValue;
+  const int route = g_open_route.load(std::memory_order_relaxed);
+  const bool able = job.salted && job.bs <= kOpenFusedMaxBs;
+  const bool wins = job.n >= kOpenFusedMinBlocks && job.bs >= kOpenFusedMinBs &&
+                    job.n * job.bs >= kOpenFusedMinBytes;
+  if (!able || route == 1 || (route == 0 && !wins)) return launch_open_composed(job, s);
+  OArgs a{};
+  a.ctext = job.ctext;
+  a.ptext = job.ptext;
+  a.n = job.n;
+  a.bs = job.bs;
+  a.last_len = job.last_len;
+  a.refs = job.refs;
+  a.status = job.status;
+  for (int i = 0; i < 8; ++i) {
+    a.salt[i] = job.salt[i];
+    a.cid_key[i] = job.cid_key[i];
+  }
+  a.cid_base = job.cid_keyed ? kKeyed : 0u;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(job.ctext) |
+                         reinterpret_cast<uintptr_t>(job.ptext) | uintptr_t(job.bs)) & 15) == 0;
+  const uint64_t C = (job.bs + 1023) >> 10;
+  if (C <= 256) return launch_open_g<1>(a, aligned, s);
+  if (C <= 512) return launch_open_g<2>(a, aligned, s);
+  if (C <= 1024) return launch_open_g<4>(a, aligned, s);
+  return launch_open_g<8>(a, aligned, s);
 }
 
 }  // namespace glfsx

@@ -165,6 +165,14 @@ class Machine:
         else:
             raise ValueError(f"can't sync unrecognized type {x.type}")
 
+    def verify(self, store, ref: Ref) -> int:
+        """fsck of the object ref names (bigblob.Machine.verify under the
+        salt of ref's type, machine.go:50-54): every blob of its tree must
+        hash to its CID and decrypt to the plaintext its DEK was derived
+        from.  Returns the number of blobs checked; raises
+        bigblob.ErrCorrupt."""
+        return self.bbag.verify(store, ref.root, salt=self.make_salt(ref.type))
+
     def get_at_path(self, store, ref: Ref, subpath: str) -> Ref:
         """tree.go:91-99 GetAtPath (ErrNoEnt when nothing is at subpath)."""
         from .tree import get_at_path

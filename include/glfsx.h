@@ -79,7 +79,8 @@ enum {
   GLFSX_E_ARG = -5,              /* invalid argument */
   GLFSX_E_UNSUPPORTED = -6,      /* e.g. block size above the kernels' limit */
   GLFSX_E_NOMEM = -7,
-  GLFSX_E_IO = -8                /* the input's read failed (io.Copy's read error) */
+  GLFSX_E_IO = -8,               /* the input's read failed (io.Copy's read error) */
+  GLFSX_E_CORRUPT = -9           /* a block failed its CID or DEK check (glfsx_open_batch) */
 };
 
 /* bigblob/blob.go:17-21 Root{Ref, Size, BlockSize} */
@@ -507,6 +508,46 @@ const char *glfsx_store_error(glfsx_store *s);
  * decrypts and downloads overlap in 64 MiB slabs. */
 int glfsx_decrypt_batch(const void *ctext, uint64_t total, uint64_t block_size,
                         const uint8_t *refs, void *ptext);
+
+/* --- verified read ------------------------------------------------------ */
+/* getF with the checks content addressing gives (ref.go:113-126; in the
+ * reference copyBlob's dst.Post, blob.go:307-315, re-hashes every copied
+ * blob on the host -- this replaces it for a pre-hashed destination).  Block
+ * j of d_ctext (block_size bytes, the last one short; block_size % 64 == 0)
+ * is checked against the 64-byte ref j of d_refs:
+ *   GLFSX_BAD_CID: BLAKE3(ctext_j) (keyed by cid_key; NULL = unkeyed) is not
+ *     the ref's CID -- the stored bytes are not the ones posted;
+ *   GLFSX_BAD_DEK: keyed-BLAKE3(salt, ChaCha20(ref's DEK) ^ ctext_j) is not
+ *     the ref's DEK -- the ref does not belong to this plaintext.  salt is
+ *     the level's salt as post took it (rawSalt for data blocks, indexSalt
+ *     for index nodes; no derivation here); NULL = no DEK check.
+ * d_status[j] (every j, no pre-zeroing needed) = the OR of the failed checks,
+ * 0 when the block is good.  The plaintext goes to d_ptext (nullable: check
+ * only; may equal d_ctext) whether or not the block is good -- the status
+ * word says whether it may be used.  One pass over the ctext where the
+ * shape allows (a salt, blocks of at most 2 MiB, enough blocks to fill the
+ * chip), the passes of the write path plus a compare otherwise; the results
+ * are identical.  Device pointers, d_refs and d_status 4-byte aligned;
+ * enqueued on stream, not synchronised. */
+#define GLFSX_BAD_CID 1u
+#define GLFSX_BAD_DEK 2u
+int glfsx_open_batch_device(const uint8_t *salt, const uint8_t *cid_key,
+                            const void *d_ctext, uint64_t total, uint64_t block_size,
+                            const void *d_refs, void *d_ptext, uint32_t *d_status,
+                            void *stream);
+/* The same over host memory, through glfsx_decrypt_batch's slabs (each
+ * slab's status words come down with its plaintext).  ptext, status_out and
+ * n_bad (the number of bad blocks) are nullable.  Returns GLFSX_E_CORRUPT if
+ * any block failed: every block has been processed and the outputs are
+ * complete by then, and glfsx_last_error names the first bad block and the
+ * checks it failed. */
+int glfsx_open_batch(const uint8_t *salt, const uint8_t *cid_key, const void *ctext,
+                     uint64_t total, uint64_t block_size, const uint8_t *refs,
+                     void *ptext, uint32_t *status_out, uint64_t *n_bad);
+/* Test hook: the route of the two calls above -- 0 auto, 1 always the
+ * composed passes, 2 the one-pass kernel wherever it is able.  Any other
+ * value changes nothing.  Returns the previous value; process-wide. */
+int glfsx_set_open_route(int route);
 
 /* --- tree shape (blob.go:219-268) -------------------------------------- */
 int glfsx_depth(uint64_t size, uint64_t block_size);
