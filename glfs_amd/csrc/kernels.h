@@ -3,7 +3,8 @@
 // gfx950 kernels: post_kernels.hip (the launches, with its fragments b3_arx.h,
 // pass_kernels.h, quad_kernels.h, one_kernels.h, small_kernels.h,
 // ragged_kernels.h, read_kernels.h and open_kernels.h holding the kernels by
-// family),
+// family; launch_plan.h the shape of a bulk launch and stream_scratch.h the
+// per-stream scratch its host half keeps, both free of device code),
 // tree_kernels.hip and
 // xof_kernels.hip (device_common.h: definitions the three share).  Not part
 // of the C-ABI.
@@ -211,8 +212,9 @@ uint32_t set_split_target(uint32_t wgs);
 // Latency-mode threshold in workgroups (see post_kernels.hip); returns the
 // previous value.
 uint32_t set_latency_wgs(uint32_t wgs);
-// Drop the split-mode scratch kept for stream s (call before destroying s,
-// after it has drained).
+// Drop all launch scratch kept for stream s on its device -- split mode,
+// k_pass_dc, k_small_q, the ragged post, the verified read -- (call before
+// destroying s, after it has drained).
 void release_stream_scratch(hipStream_t s);
 
 // Tree JSON lines on the device (tree_kernels.hip): see glfsx_tree_encode.

@@ -19,6 +19,11 @@
 //     and fuses keystream XOR, the ctext store and the CID compression, so
 //     ptext is read once per pass and ctext is never re-read.
 // Integer ALU work only (v_add3_u32 / v_xor_b32 / v_alignbit_b32); no MFMA.
+//
+// The host half below the fragments launches them.  The shape of a bulk
+// launch comes from launch_plan.h (pure functions); what a stream's launches
+// keep between them is one ScratchSlot per (device, stream) whose members
+// own their memory (stream_scratch.h).
 #include "kernels.h"
 
 #include <algorithm>
@@ -26,9 +31,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <vector>
+#include <type_traits>
 
 #include "device_common.h"
+#include "launch_plan.h"
+#include "stream_scratch.h"
 
 // One namespace block holds the fragments and the host side: closing and
 // reopening it between them changes the order in which the compiler emits
@@ -54,6 +61,17 @@ namespace {
 // glfsx_set_latency_wgs overrides it (tuning, tests of both forms).
 std::atomic<uint32_t> g_latency_wgs{512};
 uint32_t latency_wgs() { return g_latency_wgs.load(std::memory_order_relaxed); }
+
+// From a runtime g to the template parameter G: f(integral_constant<int, G>)
+// for the one of Gs that g equals, hipErrorInvalidValue when it is none.  A
+// left fold: the kernels are instantiated, and so laid out in the code
+// object, in the order of Gs (a right fold reverses them).
+template <int... Gs, class F>
+hipError_t with_g(int g, F &&f) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)(... || (g == Gs && ((e = f(std::integral_constant<int, Gs>{})), true)));
+  return e;
+}
 
 // ARX form of the launches above the latency bound: the aligned CID pass
 // with no split and G >= 4 (the headline's) runs form 1 (quarter-round
@@ -87,112 +105,65 @@ hipError_t launch_g(const KArgs &a, bool aligned, hipStream_t s) {
 // over more workgroups (fewer chunks per lane).  0 disables split mode
 // (glfsx_set_split_target: tests of both forms).
 std::atomic<uint32_t> g_split_target{2048u};
-constexpr uint32_t kMaxSplitLog2 = 8;  // the last workgroup merges <= 256 CVs
-constexpr uint64_t kDcMinWgs = 1024;   // see pass_plan
+PassPlan plan_for(uint64_t n, uint64_t maxlen) {
+  return pass_plan(n, maxlen, g_split_target.load(std::memory_order_relaxed), latency_wgs());
+}
 
-// Split-mode scratch (32 B per workgroup) and arrival counters (4 B per
-// message, zero between launches: each message's last workgroup resets its
-// own): one persistent pair of buffers per (device, stream), reused by every
-// launch on that stream -- launches on one stream are ordered, so they are
-// never shared by two in flight.  The stream-ordered pool (hipMallocAsync /
-// hipFreeAsync per launch) serialised the Writer's three-stream pipeline
-// (host round trip 43.5 -> 24 GiB/s).  A buffer only grows when a launch
-// needs more; the old one is released after its stream drains.
+// What the launches on one (device, stream) keep between them: launches on
+// one stream are ordered, so a buffer is never shared by two in flight.  The
+// stream-ordered pool (an allocation and a free per launch) serialised the
+// Writer's three-stream pipeline (host round trip 43.5 -> 24 GiB/s).  A
+// buffer only grows when a launch needs more; the old one is released after
+// its stream drains (StreamBuf::ensure).  Every member owns its memory, so
+// releasing a slot frees all of it.
 struct ScratchSlot {
-  int dev;
-  hipStream_t stream;
-  uint32_t *p;
-  size_t bytes;
-  uint32_t *cnt;
-  size_t cnt_words;
-  uint32_t *ready;     // k_pass_dc: per-message DEK ready flags (= epoch)
-  size_t ready_words;
-  uint32_t epoch;
-  uint32_t *lists;     // k_pass_dc: 2 banks of work-list counters (device)
-  uint32_t *err;       // k_pass_dc: DEK-wait timeouts (pinned host word)
-  uint32_t *d_err;     // the same word as the kernels address it
-  DcConst *dcc;        // k_pass_dc's DcConst (device memory)
-  DcConst dcc_host;    // what was last copied there
-  uint32_t *qctr;      // k_small_q: two banks of its item counter
-  uint32_t qepoch;
-  uint8_t *rplan;      // ragged post: the plan's prefixes (RArgs::pre, wpre)
-  size_t rplan_bytes;
-  uint8_t *rcv;        // ragged post: chunk and group CVs (RArgs::cvs, gcv)
-  size_t rcv_bytes;
-  uint64_t *rtot;      // ragged post: the plan's three totals (pinned host)
-  uint64_t *d_rtot;    // the same words as the kernels address them
-  uint8_t *open;       // verified read, composed route: digests, plaintext
-  size_t open_bytes;
+  StreamBuf p;         // split mode: CVs, 32 B per workgroup
+  StreamBuf cnt;       // split mode: arrival counters, 4 B per message, zero
+                       // between launches (a message's last workgroup resets its own)
+  StreamBuf ready;     // k_pass_dc: per-message DEK ready flags (= epoch)
+  uint32_t epoch = 0;
+  StreamBuf lists;     // k_pass_dc: 2 banks of work-list counters
+  PinnedBlock err;     // k_pass_dc: DEK-wait timeouts (first word)
+  StreamBuf dcc;       // k_pass_dc's DcConst
+  DcConst dcc_host{};  // what was last copied there
+  StreamBuf qctr;      // k_small_q: two banks of its item counter
+  uint32_t qepoch = 0;
+  StreamBuf rplan;     // ragged post: the plan's prefixes (RArgs::pre, wpre)
+  StreamBuf rcv;       // ragged post: chunk and group CVs (RArgs::cvs, gcv)
+  PinnedBlock rtot;    // ragged post: the plan's three totals
+  StreamBuf open;      // verified read, composed route: digests, plaintext
 };
+// g_scratch_mu guards the registry and every slot, and is held across a
+// getter's whole body, the drain of a growing buffer included: narrowing it
+// would change behaviour.  Never destroyed: its slots would free through a
+// HIP runtime that may be gone at exit.
 std::mutex g_scratch_mu;
-std::vector<ScratchSlot> g_scratch;
+StreamRegistry<ScratchSlot> &g_scratch = *new StreamRegistry<ScratchSlot>();
 
-// The device stream s belongs to (the current device for the null stream),
-// current for the scope.  The scratch slots are keyed by (device, stream)
-// and allocated on the current device; a caller driving several GPUs may
-// reach here with another device current than its stream's (a
-// multi-device Writer checked a lane's error word under the wrong device
-// and missed it), so the stream, not the thread, names the device.
-struct StreamDevice {
-  int dev = 0, prev = 0;
-  hipError_t e = hipSuccess;
-  explicit StreamDevice(hipStream_t s) {
-    e = hipGetDevice(&prev);
-    if (e != hipSuccess) return;
-    dev = prev;
-    hipDevice_t d = 0;
-    if (s && hipStreamGetDevice(s, &d) == hipSuccess) dev = d;
-    if (dev != prev) e = hipSetDevice(dev);
-  }
-  ~StreamDevice() {
-    if (dev != prev) (void)hipSetDevice(prev);
+// A getter's common start: s's device made current, the lock taken and the
+// slot of (device, s) found or made.
+struct SlotLock {
+  StreamDevice sd;
+  std::unique_lock<std::mutex> lk;
+  ScratchSlot *sl = nullptr;
+  explicit SlotLock(hipStream_t s, bool make = true) : sd(s) {
+    if (sd.e != hipSuccess) return;
+    lk = std::unique_lock<std::mutex>(g_scratch_mu);
+    sl = make ? g_scratch.find_or_make(sd.dev, s) : g_scratch.find(sd.dev, s);
   }
 };
 
+// Split-mode scratch for wgs workgroups and msgs messages.
 hipError_t scratch_get(KArgs *a, uint64_t wgs, uint64_t msgs, hipStream_t s) {
-  const size_t bytes = size_t(wgs) * 32, words = size_t(msgs);
-  StreamDevice sd(s);
-  if (sd.e != hipSuccess) return sd.e;
-  const int dev = sd.dev;
-  hipError_t e = hipSuccess;
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  ScratchSlot *sl = nullptr;
-  for (ScratchSlot &x : g_scratch)
-    if (x.dev == dev && x.stream == s) sl = &x;
-  if (!sl) {
-    g_scratch.push_back({dev, s, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr,
-                         nullptr, nullptr, nullptr, DcConst{}, nullptr, 0});
-    sl = &g_scratch.back();
-  }
-  if (sl->bytes < bytes || sl->cnt_words < words) {
-    if (sl->p || sl->cnt) {
-      e = hipStreamSynchronize(s);
-      if (e != hipSuccess) return e;
-    }
-    if (sl->bytes < bytes) {
-      if (sl->p) (void)hipFree(sl->p);
-      sl->p = nullptr;
-      sl->bytes = 0;
-      // at least the default target's worst case, so it rarely grows
-      const size_t want = std::max(bytes, size_t(2) << 16);
-      e = hipMalloc(reinterpret_cast<void **>(&sl->p), want);
-      if (e != hipSuccess) return e;
-      sl->bytes = want;
-    }
-    if (sl->cnt_words < words) {
-      if (sl->cnt) (void)hipFree(sl->cnt);
-      sl->cnt = nullptr;
-      sl->cnt_words = 0;
-      const size_t want = std::max(words, size_t(4096));
-      e = hipMalloc(reinterpret_cast<void **>(&sl->cnt), want * 4);
-      if (e != hipSuccess) return e;
-      e = hipMemsetAsync(sl->cnt, 0, want * 4, s);
-      if (e != hipSuccess) return e;
-      sl->cnt_words = want;
-    }
-  }
-  a->scratch = sl->p;
-  a->cnt = sl->cnt;
+  SlotLock g(s);
+  if (g.sd.e != hipSuccess) return g.sd.e;
+  // at least the default target's worst case, so it rarely grows
+  hipError_t e = g.sl->p.ensure(s, size_t(wgs) * 32, size_t(2) << 16, 0, false);
+  if (e != hipSuccess) return e;
+  e = g.sl->cnt.ensure(s, size_t(msgs) * 4, 4096 * 4, 0, true);
+  if (e != hipSuccess) return e;
+  a->scratch = g.sl->p.as<uint32_t>();
+  a->cnt = g.sl->cnt.as<uint32_t>();
   return hipSuccess;
 }
 
@@ -207,52 +178,24 @@ std::atomic<uint64_t> g_dc_timeouts{0};
 constexpr size_t kListWords = 2 * kLists * kListStride;
 
 hipError_t dc_get(uint64_t msgs, hipStream_t s, DcState *d) {
-  StreamDevice sd(s);
-  if (sd.e != hipSuccess) return sd.e;
-  const int dev = sd.dev;
-  hipError_t e = hipSuccess;
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  ScratchSlot *sl = nullptr;
-  for (ScratchSlot &x : g_scratch)
-    if (x.dev == dev && x.stream == s) sl = &x;
-  if (!sl) return hipErrorInvalidValue;  // scratch_get first
-  if (!sl->lists) {
-    e = hipMalloc(reinterpret_cast<void **>(&sl->lists), kListWords * 4);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(sl->lists, 0, kListWords * 4, s);
-    if (e != hipSuccess) return e;
-    void *h = nullptr, *dp = nullptr;
-    e = hipHostMalloc(&h, 64, hipHostMallocCoherent);
-    if (e != hipSuccess) return e;
-    e = hipHostGetDevicePointer(&dp, h, 0);
-    if (e != hipSuccess) {
-      (void)hipHostFree(h);
-      return e;
-    }
-    sl->err = static_cast<uint32_t *>(h);
-    sl->d_err = static_cast<uint32_t *>(dp);
-    __atomic_store_n(sl->err, 0u, __ATOMIC_RELAXED);
-  }
-  if (sl->ready_words < msgs) {
-    if (sl->ready) {
-      e = hipStreamSynchronize(s);
-      if (e != hipSuccess) return e;
-      (void)hipFree(sl->ready);
-    }
-    sl->ready = nullptr;
-    sl->ready_words = 0;
-    const size_t want = std::max<size_t>(msgs, 4096);
-    e = hipMalloc(reinterpret_cast<void **>(&sl->ready), want * 4);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(sl->ready, 0, want * 4, s);
-    if (e != hipSuccess) return e;
-    sl->ready_words = want;  // the epoch goes on: the new flags are zero
-  }
-  DcConst want{sl->ready, sl->lists, sl->d_err,
+  SlotLock g(s);
+  if (g.sd.e != hipSuccess) return g.sd.e;
+  ScratchSlot *sl = g.sl;
+  // each piece on its own: a failure leaves that piece empty, and the next
+  // call makes exactly what is missing
+  hipError_t e = sl->lists.ensure(s, kListWords * 4, kListWords * 4, 0, true);
+  if (e != hipSuccess) return e;
+  e = sl->err.ensure();
+  if (e != hipSuccess) return e;
+  // when the flags grow the epoch goes on: the new flags are zero
+  e = sl->ready.ensure(s, size_t(msgs) * 4, 4096 * 4, 0, true);
+  if (e != hipSuccess) return e;
+  DcConst want{sl->ready.as<uint32_t>(), sl->lists.as<uint32_t>(),
+               static_cast<uint32_t *>(sl->err.d),
                g_dc_wait_ticks.load(std::memory_order_relaxed),
                g_dc_skip_msg.exchange(~0u, std::memory_order_relaxed)};
-  if (!sl->dcc) {
-    e = hipMalloc(reinterpret_cast<void **>(&sl->dcc), sizeof(DcConst));
+  if (!sl->dcc.p) {
+    e = sl->dcc.ensure(s, sizeof(DcConst), sizeof(DcConst), 0, false);
     if (e != hipSuccess) return e;
     sl->dcc_host = DcConst{};
   }
@@ -261,7 +204,7 @@ hipError_t dc_get(uint64_t msgs, hipStream_t s, DcState *d) {
       want.wait_ticks != h.wait_ticks || want.skip_msg != h.skip_msg) {
     // rare (new buffers, a test hook): ordered on s before the launch; the
     // copy is staged from pageable memory, so `want` may go out of scope
-    e = hipMemcpyAsync(sl->dcc, &want, sizeof want, hipMemcpyHostToDevice, s);
+    e = hipMemcpyAsync(sl->dcc.p, &want, sizeof want, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return e;
     e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
@@ -273,72 +216,21 @@ hipError_t dc_get(uint64_t msgs, hipStream_t s, DcState *d) {
   // Zero is never an epoch; the bank parity must alternate across the wrap.
   if (++sl->epoch == 0) sl->epoch = 2;
   d->epoch = sl->epoch;
-  d->c = sl->dcc;
+  d->c = sl->dcc.as<DcConst>();
   return hipSuccess;
 }
 
+// Both banks of s's work-list counters start over at zero.
+void dc_lists_zero(ScratchSlot *sl, hipStream_t s) {
+  if (sl && sl->lists.p) (void)hipMemsetAsync(sl->lists.p, 0, kListWords * 4, s);
+}
+
 // A k_pass_dc launch failed after dc_get: its epoch was used without the
-// launch that clears the next bank, so both banks start over at zero.
+// launch that clears the next bank.
 void dc_launch_failed(hipStream_t s) {
-  StreamDevice sd(s);
-  if (sd.e != hipSuccess) return;
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  for (ScratchSlot &x : g_scratch)
-    if (x.dev == sd.dev && x.stream == s && x.lists)
-      (void)hipMemsetAsync(x.lists, 0, kListWords * 4, s);
+  SlotLock g(s, false);
+  dc_lists_zero(g.sl, s);
 }
-
-// Chunks per lane (g) and log2 workgroups per message (sl) of a launch over
-// n messages of at most maxlen bytes.
-void pass_plan(uint64_t n, uint64_t maxlen, int *g_out, uint32_t *sl_out) {
-  const uint64_t C = maxlen ? (maxlen + 1023) >> 10 : 1;
-  int g = 1;
-  while (256ull * g < C && g < 64) g *= 2;
-  // messages above 256 lanes x 64 chunks (16 MiB) always span several
-  // workgroups
-  uint32_t sl = 0;
-  while ((256ull * g << sl) < C) ++sl;
-  // few messages: halve the chunks per lane and double the workgroups per
-  // message until the launch fills the chip (256 CUs x 8 workgroups)
-  const uint64_t target = g_split_target.load(std::memory_order_relaxed);
-  const int g0 = g;
-  const uint32_t sl0 = sl;
-  while (g > 1 && sl < kMaxSplitLog2 && (n << sl) < target) {
-    g /= 2;
-    ++sl;
-  }
-  // ... but a one-launch split post (k_pass_dc: more than latency_wgs * 5/8
-  // workgroups, G <= 4) of fewer than ~1024 workgroups runs its DEK and CID
-  // items in about one round each and loses to the two-pass latency form:
-  // take the plan with the most workgroups that stays in that form.  Create
-  // at 2 MiB blocks, 64 / 115 blocks (the config-4 tree blob): 355 -> 499 /
-  // 546 -> 590 GiB/s; 128 x 1 MiB 362 -> 506; 200 x 2 MiB and up, or 256 x
-  // 1 MiB and up, keep the one-launch plan (scripts/r4_plan_sweep.py,
-  // DESIGN.md section 5)
-  const uint64_t lat = uint64_t(g_latency_wgs.load(std::memory_order_relaxed)) * 5 / 8;
-  if (sl > 0 && g <= 4 && (n << sl) > lat && (n << sl) < kDcMinWgs) {
-    int bg = 0;
-    uint32_t bsl = 0;
-    for (int gg = g0, s = int(sl0); gg >= 1 && s <= int(kMaxSplitLog2); gg /= 2, ++s)
-      if ((n << s) <= lat) {
-        bg = gg;
-        bsl = uint32_t(s);
-      }
-    if (bg && bsl > 0) {
-      g = bg;
-      sl = bsl;
-    }
-  }
-  *g_out = g;
-  *sl_out = sl;
-}
-
-// BLAKE3-only pass in quad layout (k_quad): latency-bound launches of at
-// most 16384 chunks, messages of at most 64 x 256 KiB.  Messages of up to
-// 64 x 64 KiB (4 MiB: index nodes at 1-4 MiB blocks) use 64 quads per
-// workgroup, larger ones 256 (the last workgroup merges <= 64 CVs, one per
-// quad of its own).
-int quad_qpw(uint64_t maxlen) { return maxlen <= (64ull << 16) ? 64 : 256; }
 
 hipError_t launch_quad(KArgs a, uint64_t maxlen, hipStream_t s) {
   const int qpw = quad_qpw(maxlen);
@@ -371,9 +263,7 @@ bool quad_ok(const KArgs &a, uint64_t maxlen, bool aligned, uint32_t sl) {
 template <bool CHACHA>
 hipError_t launch_pass(KArgs a, uint64_t maxlen, bool aligned,
                        hipStream_t s) {
-  int g;
-  uint32_t sl;
-  pass_plan(a.n, maxlen, &g, &sl);
+  const auto [g, sl] = plan_for(a.n, maxlen);
   if constexpr (!CHACHA) {
     if (quad_ok(a, maxlen, aligned, sl)) return launch_quad(a, maxlen, s);
   }
@@ -384,44 +274,18 @@ hipError_t launch_pass(KArgs a, uint64_t maxlen, bool aligned,
     hipError_t e = scratch_get(&a, a.n << sl, a.n, s);
     if (e != hipSuccess) return e;
   }
-  hipError_t e;
-  switch (g) {
-    case 1: e = launch_g<1, CHACHA>(a, aligned, s); break;
-    case 2: e = launch_g<2, CHACHA>(a, aligned, s); break;
-    case 4: e = launch_g<4, CHACHA>(a, aligned, s); break;
-    case 8: e = launch_g<8, CHACHA>(a, aligned, s); break;
-    case 16: e = launch_g<16, CHACHA>(a, aligned, s); break;
-    case 32: e = launch_g<32, CHACHA>(a, aligned, s); break;
-    case 64: e = launch_g<64, CHACHA>(a, aligned, s); break;
-    default: e = hipErrorInvalidValue;
-  }
-  return e;
+  return with_g<1, 2, 4, 8, 16, 32, 64>(
+      g, [&](auto G) { return launch_g<G(), CHACHA>(a, aligned, s); });
 }
 
-// k_small_q's counter banks on stream s (current device) and this launch's
-// epoch.
+// k_small_q's counter banks on stream s and this launch's epoch.
 hipError_t small_q_get(hipStream_t s, uint32_t **ctr, uint32_t *epoch) {
-  StreamDevice sd(s);
-  if (sd.e != hipSuccess) return sd.e;
-  const int dev = sd.dev;
-  hipError_t e = hipSuccess;
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  ScratchSlot *sl = nullptr;
-  for (ScratchSlot &x : g_scratch)
-    if (x.dev == dev && x.stream == s) sl = &x;
-  if (!sl) {
-    g_scratch.push_back({dev, s, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr,
-                         nullptr, nullptr, nullptr, DcConst{}, nullptr, 0});
-    sl = &g_scratch.back();
-  }
-  if (!sl->qctr) {
-    e = hipMalloc(reinterpret_cast<void **>(&sl->qctr), 64 * 4);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(sl->qctr, 0, 64 * 4, s);
-    if (e != hipSuccess) return e;
-  }
-  *ctr = sl->qctr;
-  *epoch = ++sl->qepoch;
+  SlotLock g(s);
+  if (g.sd.e != hipSuccess) return g.sd.e;
+  hipError_t e = g.sl->qctr.ensure(s, 64 * 4, 64 * 4, 0, true);
+  if (e != hipSuccess) return e;
+  *ctr = g.sl->qctr.as<uint32_t>();
+  *epoch = ++g.sl->qepoch;
   return hipSuccess;
 }
 
@@ -464,31 +328,19 @@ hipError_t launch_small_pass(const SArgs &a, uint64_t max_len, hipStream_t s) {
   const uint64_t C = max_len ? (max_len + 1023) >> 10 : 1;
   const dim3 grid(uint32_t((a.n + 255) / 256)), block(256);
   const int gsel = C <= 1 ? 1 : C <= 2 ? 2 : C <= 4 ? 4 : C <= 8 ? 8 : C <= 16 ? 16 : 0;
-  if (grid.x <= latency_wgs()) {  // few blobs: the compiler's ARX form
-    switch (gsel) {
-      case 1: hipLaunchKernelGGL((k_small<1, CHACHA, false>), grid, block, 0, s, a); break;
-      case 2: hipLaunchKernelGGL((k_small<2, CHACHA, false>), grid, block, 0, s, a); break;
-      case 4: hipLaunchKernelGGL((k_small<4, CHACHA, false>), grid, block, 0, s, a); break;
-      case 8: hipLaunchKernelGGL((k_small<8, CHACHA, false>), grid, block, 0, s, a); break;
-      case 16: hipLaunchKernelGGL((k_small<16, CHACHA, false>), grid, block, 0, s, a); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
+  if (grid.x <= latency_wgs())  // few blobs: the compiler's ARX form
+    return with_g<1, 2, 4, 8, 16>(gsel, [&](auto G) {
+      hipLaunchKernelGGL((k_small<G(), CHACHA, false>), grid, block, 0, s, a);
+      return hipGetLastError();
+    });
   // more workgroups than the chip holds: per-wave items (k_small_q).  The
   // CID pass runs ARX form 1 (quarter-round order), as the headline's CID
   // pass: 928.8 vs 913.3 GiB/s small blobs, config 4 798.1 vs 787.3 (3
   // interleaved reps, after the wave-offset fix; round 2 measured form 2
   // ahead when half the waves took the per-lane path); the DEK pass form 2
   constexpr int F = CHACHA ? 1 : 2;
-  switch (gsel) {
-    case 1: return launch_small_q<1, CHACHA, F>(a, s);
-    case 2: return launch_small_q<2, CHACHA, F>(a, s);
-    case 4: return launch_small_q<4, CHACHA, F>(a, s);
-    case 8: return launch_small_q<8, CHACHA, F>(a, s);
-    case 16: return launch_small_q<16, CHACHA, F>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_g<1, 2, 4, 8, 16>(
+      gsel, [&](auto G) { return launch_small_q<G(), CHACHA, F>(a, s); });
 }
 
 // The clock probe (g_clk): off until clock_probe is first called.
@@ -543,48 +395,22 @@ uint32_t set_split_target(uint32_t wgs) { return g_split_target.exchange(wgs); }
 uint32_t set_latency_wgs(uint32_t wgs) { return g_latency_wgs.exchange(wgs); }
 
 void release_stream_scratch(hipStream_t s) {
-  StreamDevice sd(s);
-  if (sd.e != hipSuccess) return;
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  for (size_t i = 0; i < g_scratch.size(); ++i) {
-    if (g_scratch[i].stream != s) continue;
-    if (sd.dev == g_scratch[i].dev) {
-      if (g_scratch[i].p) (void)hipFree(g_scratch[i].p);
-      if (g_scratch[i].cnt) (void)hipFree(g_scratch[i].cnt);
-      if (g_scratch[i].ready) (void)hipFree(g_scratch[i].ready);
-      if (g_scratch[i].lists) (void)hipFree(g_scratch[i].lists);
-      if (g_scratch[i].err) (void)hipHostFree(g_scratch[i].err);
-      if (g_scratch[i].dcc) (void)hipFree(g_scratch[i].dcc);
-      if (g_scratch[i].qctr) (void)hipFree(g_scratch[i].qctr);
-      if (g_scratch[i].rplan) (void)hipFree(g_scratch[i].rplan);
-      if (g_scratch[i].rcv) (void)hipFree(g_scratch[i].rcv);
-      if (g_scratch[i].rtot) (void)hipHostFree(g_scratch[i].rtot);
-      if (g_scratch[i].open) (void)hipFree(g_scratch[i].open);
-    } else {
-      continue;  // another device's stream of the same handle value
-    }
-    g_scratch[i] = g_scratch.back();
-    g_scratch.pop_back();
-    --i;
-  }
+  SlotLock g(s, false);
+  if (g.sl) g_scratch.release(g.sd.dev, s);
 }
 
 uint32_t fused_errors_take(hipStream_t s) {
-  StreamDevice sd(s);
-  if (sd.e != hipSuccess) return 0;
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  for (ScratchSlot &x : g_scratch)
-    if (x.dev == sd.dev && x.stream == s && x.err) {
-      const uint32_t v = __atomic_exchange_n(x.err, 0u, __ATOMIC_ACQ_REL);
-      if (v) {
-        g_dc_timeouts.fetch_add(1, std::memory_order_relaxed);
-        // a failed launch may leave its counters off zero (it zeroes the
-        // other bank); both banks start over at zero
-        (void)hipMemsetAsync(x.lists, 0, kListWords * 4, s);
-      }
-      return v;
-    }
-  return 0;
+  SlotLock g(s, false);
+  if (!g.sl || !g.sl->err.h) return 0;
+  const uint32_t v =
+      __atomic_exchange_n(static_cast<uint32_t *>(g.sl->err.h), 0u, __ATOMIC_ACQ_REL);
+  if (v) {
+    g_dc_timeouts.fetch_add(1, std::memory_order_relaxed);
+    // a failed launch may leave its counters off zero (it zeroes the other
+    // bank)
+    dc_lists_zero(g.sl, s);
+  }
+  return v;
 }
 
 void fused_debug(uint32_t skip_msg, uint64_t wait_us) {
@@ -622,9 +448,9 @@ hipError_t launch_post_fused(const PostJob &job, hipStream_t s, bool *done) {
   if (job.n < 2 || !is_aligned(job)) return hipSuccess;
   if ((reinterpret_cast<uintptr_t>(job.out.refs) | job.out.stride) & 3) return hipSuccess;
   const uint64_t maxlen = std::max(job.msg_len, job.last_len);
-  int g;
-  uint32_t sl;
-  pass_plan(job.n, maxlen, &g, &sl);
+  const PassPlan plan = plan_for(job.n, maxlen);
+  const int g = plan.g;
+  const uint32_t sl = plan.sl;
   const uint64_t wgs = job.n << sl;
   // launches of 320-512 workgroups (default threshold) also run fused in the
   // many-wave form: Create of 96 / 128 MiB at 1 MiB blocks (384 / 512
@@ -663,13 +489,11 @@ hipError_t launch_post_fused(const PostJob &job, hipStream_t s, bool *done) {
     items += dc_list_items(m, dc_list_fine(m, d.fine_div), sl);
   }
   const dim3 grid{uint32_t(items)}, block{256};
-  switch (g) {
-    case 1: hipLaunchKernelGGL(k_pass_dc<1>, grid, block, 0, s, a, b, c, d); break;
-    case 2: hipLaunchKernelGGL(k_pass_dc<2>, grid, block, 0, s, a, b, c, d); break;
-    default: hipLaunchKernelGGL(k_pass_dc<4>, grid, block, 0, s, a, b, c, d); break;
-  }
+  e = with_g<1, 2, 4>(g, [&](auto G) {
+    hipLaunchKernelGGL(k_pass_dc<G()>, grid, block, 0, s, a, b, c, d);
+    return hipGetLastError();
+  });
   *done = true;
-  e = hipGetLastError();
   if (e != hipSuccess) dc_launch_failed(s);
   return e;
 }
@@ -692,9 +516,7 @@ hipError_t launch_cid_pass(const PostJob &job, hipStream_t s) {
   a.out_off = 0;
   const uint64_t maxlen = job.n > 1 ? std::max(job.msg_len, job.last_len)
                                     : job.last_len;
-  int g;
-  uint32_t sl;
-  pass_plan(job.n, maxlen, &g, &sl);
+  const uint32_t sl = plan_for(job.n, maxlen).sl;
   // Latency-bound launches (index nodes, single posts, small batches): the
   // fused pass leaves one wave per SIMD running ChaCha20 and BLAKE3 in
   // series.  The keystream has no chaining, so instead every 64-B block gets
@@ -769,59 +591,26 @@ hipError_t launch_post_small(const SmallJob &job, hipStream_t s) {
   return launch_small_pass<true>(a, max_len, s);
 }
 
+// The buffers sized by a call's data (ragged post, verified read) start at
+// 1 MiB and grow with a quarter of headroom.
+constexpr size_t kGrowFloor = size_t(1) << 20;
+
 // The ragged post's buffers on stream s: `plan` / `cv` bytes (0: leave that
-// one alone), grown when needed -- after the stream has drained -- and the
-// pinned words for the plan's totals.
+// one alone) and the pinned words for the plan's totals.
 static hipError_t rag_get(hipStream_t s, size_t plan, size_t cv, uint8_t **d_plan,
                           uint8_t **d_cv, uint64_t **tot, uint64_t **d_tot) {
-  StreamDevice sd(s);
-  if (sd.e != hipSuccess) return sd.e;
-  const int dev = sd.dev;
-  hipError_t e = hipSuccess;
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  ScratchSlot *sl = nullptr;
-  for (ScratchSlot &x : g_scratch)
-    if (x.dev == dev && x.stream == s) sl = &x;
-  if (!sl) {
-    g_scratch.push_back(ScratchSlot{});
-    sl = &g_scratch.back();
-    sl->dev = dev;
-    sl->stream = s;
-  }
-  if (!sl->rtot) {
-    void *h = nullptr, *dp = nullptr;
-    e = hipHostMalloc(&h, 64, hipHostMallocCoherent);
-    if (e != hipSuccess) return e;
-    e = hipHostGetDevicePointer(&dp, h, 0);
-    if (e != hipSuccess) {
-      (void)hipHostFree(h);
-      return e;
-    }
-    sl->rtot = static_cast<uint64_t *>(h);
-    sl->d_rtot = static_cast<uint64_t *>(dp);
-  }
-  struct Grow {
-    uint8_t **p;
-    size_t *have, want;
-  } grow[2] = {{&sl->rplan, &sl->rplan_bytes, plan}, {&sl->rcv, &sl->rcv_bytes, cv}};
-  for (const Grow &g : grow) {
-    if (*g.have >= g.want) continue;
-    if (*g.p) {
-      e = hipStreamSynchronize(s);
-      if (e != hipSuccess) return e;
-      (void)hipFree(*g.p);
-    }
-    *g.p = nullptr;
-    *g.have = 0;
-    const size_t want = std::max(g.want + g.want / 4, size_t(1) << 20);
-    e = hipMalloc(reinterpret_cast<void **>(g.p), want);
-    if (e != hipSuccess) return e;
-    *g.have = want;
-  }
-  *d_plan = sl->rplan;
-  *d_cv = sl->rcv;
-  *tot = sl->rtot;
-  *d_tot = sl->d_rtot;
+  SlotLock g(s);
+  if (g.sd.e != hipSuccess) return g.sd.e;
+  hipError_t e = g.sl->rtot.ensure();
+  if (e != hipSuccess) return e;
+  e = g.sl->rplan.ensure(s, plan, kGrowFloor, 4, false);
+  if (e != hipSuccess) return e;
+  e = g.sl->rcv.ensure(s, cv, kGrowFloor, 4, false);
+  if (e != hipSuccess) return e;
+  *d_plan = g.sl->rplan.as<uint8_t>();
+  *d_cv = g.sl->rcv.as<uint8_t>();
+  *tot = static_cast<uint64_t *>(g.sl->rtot.h);
+  *d_tot = static_cast<uint64_t *>(g.sl->rtot.d);
   return hipSuccess;
 }
 
@@ -1070,36 +859,13 @@ constexpr uint64_t kOpenFusedMinBs = 256ull << 10;
 constexpr uint64_t kOpenFusedMinBytes = 1ull << 30;
 constexpr uint64_t kOpenFusedMaxBs = 2ull << 20;  // 256 lanes x 8 chunks
 
-// The composed route's scratch on stream s: `bytes`, grown when needed after
-// the stream has drained.
+// The composed route's scratch on stream s: `bytes`.
 static hipError_t open_get(hipStream_t s, size_t bytes, uint8_t **p) {
-  StreamDevice sd(s);
-  if (sd.e != hipSuccess) return sd.e;
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  ScratchSlot *sl = nullptr;
-  for (ScratchSlot &x : g_scratch)
-    if (x.dev == sd.dev && x.stream == s) sl = &x;
-  if (!sl) {
-    g_scratch.push_back(ScratchSlot{});
-    sl = &g_scratch.back();
-    sl->dev = sd.dev;
-    sl->stream = s;
-  }
-  if (sl->open_bytes < bytes) {
-    if (sl->open) {
-      hipError_t e = hipStreamSynchronize(s);
-      if (e != hipSuccess) return e;
-      (void)hipFree(sl->open);
-    }
-    sl->open = nullptr;
-    sl->open_bytes = 0;
-    const size_t want = std::max(bytes + bytes / 4, size_t(1) << 20);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&sl->open), want);
-    if (e != hipSuccess) return e;
-    sl->open_bytes = want;
-  }
-  *p = sl->open;
-  return hipSuccess;
+  SlotLock g(s);
+  if (g.sd.e != hipSuccess) return g.sd.e;
+  hipError_t e = g.sl->open.ensure(s, bytes, kGrowFloor, 4, false);
+  *p = g.sl->open.as<uint8_t>();
+  return e;
 }
 
 template <int G>
@@ -1176,10 +942,8 @@ hipError_t launch_open(const OpenJob &job, hipStream_t s) {
   const bool aligned = ((reinterpret_cast<uintptr_t>(job.ctext) |
                          reinterpret_cast<uintptr_t>(job.ptext) | uintptr_t(job.bs)) & 15) == 0;
   const uint64_t C = (job.bs + 1023) >> 10;
-  if (C <= 256) return launch_open_g<1>(a, aligned, s);
-  if (C <= 512) return launch_open_g<2>(a, aligned, s);
-  if (C <= 1024) return launch_open_g<4>(a, aligned, s);
-  return launch_open_g<8>(a, aligned, s);
+  const int g = C <= 256 ? 1 : C <= 512 ? 2 : C <= 1024 ? 4 : 8;
+  return with_g<1, 2, 4, 8>(g, [&](auto G) { return launch_open_g<G()>(a, aligned, s); });
 }
 
 }  // namespace glfsx

@@ -1,0 +1,331 @@
+// The launch layer's per-stream scratch (glfs_amd/csrc/stream_scratch.h) and
+// launch plans (launch_plan.h), stand-alone.  Built by tests/test_host_units.py
+// with the host compiler under -fsanitize=address,undefined.  No HIP library
+// is linked: the few runtime entry points the header calls are fakes over
+// malloc, defined here, that log their calls and fail on request.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <set>
+#include <string>
+
+#include "launch_plan.h"
+#include "stream_scratch.h"
+
+using namespace glfsx;
+
+static int g_failed = 0;
+#define CHECK(cond)                                                  \
+  do {                                                               \
+    if (!(cond)) {                                                   \
+      fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #cond); \
+      ++g_failed;                                                    \
+    }                                                                \
+  } while (0)
+
+// ---- the fake runtime ----
+struct Fake {
+  std::string log;  // one letter per call: M malloc, F free, H host malloc,
+                    // h host free, P device pointer, Z memset, S synchronize
+  std::map<char, int> fail;  // fail the k-th call from now of that letter
+  std::set<void *> dev, pin;  // live allocations
+  int mallocs = 0, frees = 0, host_mallocs = 0, host_frees = 0;
+  size_t last_malloc = 0, last_memset = 0;
+  void *last_memset_p = nullptr;
+  hipStream_t last_memset_stream = nullptr, last_sync_stream = nullptr;
+  unsigned last_host_flags = 0;
+  int cur = 0;
+  std::map<hipStream_t, int> stream_dev;
+  std::string set_device_log;
+  bool call(char c) {  // false: this call is to fail
+    log += c;
+    auto it = fail.find(c);
+    return it == fail.end() || --it->second != 0 || (fail.erase(it), false);
+  }
+};
+static Fake F;
+static hipStream_t stream(uintptr_t i) { return reinterpret_cast<hipStream_t>(i << 4); }
+
+extern "C" {
+hipError_t hipMalloc(void **p, size_t n) {
+  if (!F.call('M')) return hipErrorOutOfMemory;
+  *p = malloc(n);
+  F.dev.insert(*p);
+  ++F.mallocs;
+  F.last_malloc = n;
+  return hipSuccess;
+}
+hipError_t hipFree(void *p) {
+  F.call('F');
+  CHECK(F.dev.erase(p) == 1);  // live, and freed once
+  free(p);
+  ++F.frees;
+  return hipSuccess;
+}
+hipError_t hipHostMalloc(void **p, size_t n, unsigned int flags) {
+  if (!F.call('H')) return hipErrorOutOfMemory;
+  *p = malloc(n);
+  memset(*p, 0xa5, n);
+  F.pin.insert(*p);
+  ++F.host_mallocs;
+  F.last_host_flags = flags;
+  return hipSuccess;
+}
+hipError_t hipHostFree(void *p) {
+  F.call('h');
+  CHECK(F.pin.erase(p) == 1);
+  free(p);
+  ++F.host_frees;
+  return hipSuccess;
+}
+hipError_t hipHostGetDevicePointer(void **d, void *h, unsigned int) {
+  if (!F.call('P')) return hipErrorInvalidValue;
+  CHECK(F.pin.count(h) == 1);
+  *d = h;
+  return hipSuccess;
+}
+hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t s) {
+  if (!F.call('Z')) return hipErrorInvalidValue;
+  CHECK(F.dev.count(p) == 1);
+  memset(p, v, n);  // out of bounds: the sanitizer reports it
+  F.last_memset = n;
+  F.last_memset_p = p;
+  F.last_memset_stream = s;
+  return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t s) {
+  F.last_sync_stream = s;
+  return F.call('S') ? hipSuccess : hipErrorUnknown;
+}
+hipError_t hipGetDevice(int *d) {
+  *d = F.cur;
+  return hipSuccess;
+}
+hipError_t hipSetDevice(int d) {
+  F.cur = d;
+  F.set_device_log += char('0' + d);
+  return hipSuccess;
+}
+hipError_t hipStreamGetDevice(hipStream_t s, hipDevice_t *d) {
+  auto it = F.stream_dev.find(s);
+  if (it == F.stream_dev.end()) return hipErrorInvalidHandle;
+  *d = it->second;
+  return hipSuccess;
+}
+}
+
+static void test_ensure() {
+  F = Fake{};
+  const hipStream_t s = stream(1);
+  {
+    StreamBuf b;
+    // first allocation: no drain; the floor; not zeroed
+    CHECK(b.ensure(s, 100, 128 << 10, 0, false) == hipSuccess);
+    CHECK(F.log == "M" && b.p && b.cap == (128u << 10) && F.last_malloc == b.cap);
+    // capacity suffices: no call
+    CHECK(b.ensure(s, 128 << 10, 128 << 10, 0, false) == hipSuccess && F.log == "M");
+    CHECK(b.ensure(s, 0, 0, 0, true) == hipSuccess && F.log == "M");
+    // growth: drain, free, allocate; above the floor the size asked for
+    CHECK(b.ensure(s, (128 << 10) + 1, 128 << 10, 0, false) == hipSuccess);
+    CHECK(F.log == "MSFM" && F.last_sync_stream == s && b.cap == (128u << 10) + 1);
+    // moved: the source is empty, one owner
+    StreamBuf c(std::move(b));
+    CHECK(!b.p && b.cap == 0 && c.p && c.cap == (128u << 10) + 1);
+    b = std::move(c);
+    CHECK(!c.p && b.p && F.log == "MSFM");
+  }
+  CHECK(F.log == "MSFMF" && F.dev.empty());
+  {
+    // zeroed buffers: the memset covers the whole new allocation, on s
+    F = Fake{};
+    StreamBuf cnt;
+    CHECK(cnt.ensure(s, 10 * 4, 4096 * 4, 0, true) == hipSuccess);
+    CHECK(F.log == "MZ" && cnt.cap == 4096 * 4 && F.last_memset == cnt.cap);
+    CHECK(F.last_memset_p == cnt.p && F.last_memset_stream == s);
+    CHECK(cnt.ensure(s, 5000 * 4, 4096 * 4, 0, true) == hipSuccess);
+    CHECK(F.log == "MZSFMZ" && cnt.cap == 5000 * 4 && F.last_memset == 5000 * 4);
+    // "zeroed once": the floor is the size, the second call does nothing
+    StreamBuf q;
+    CHECK(q.ensure(s, 64 * 4, 64 * 4, 0, true) == hipSuccess && q.cap == 256);
+    const std::string l = F.log;
+    CHECK(q.ensure(s, 64 * 4, 64 * 4, 0, true) == hipSuccess && F.log == l);
+    // a quarter of headroom, 1 MiB floor
+    StreamBuf r;
+    CHECK(r.ensure(s, 1000, 1 << 20, 4, false) == hipSuccess && r.cap == (1u << 20));
+    CHECK(r.ensure(s, 4 << 20, 1 << 20, 4, false) == hipSuccess && r.cap == (5u << 20));
+    CHECK(r.ensure(s, 5 << 20, 1 << 20, 4, false) == hipSuccess && r.cap == (5u << 20));
+    // just under the floor with headroom: the floor; just over: the sum
+    StreamBuf t;
+    CHECK(t.ensure(s, 800 << 10, 1 << 20, 4, false) == hipSuccess && t.cap == (1u << 20));
+    StreamBuf u;
+    CHECK(u.ensure(s, 900 << 10, 1 << 20, 4, false) == hipSuccess && u.cap == (1125u << 10));
+  }
+  CHECK(F.dev.empty() && F.mallocs == F.frees);
+}
+
+static void test_failures() {
+  F = Fake{};
+  const hipStream_t s = stream(2);
+  {
+    StreamBuf b;
+    F.fail['M'] = 1;  // the first allocation
+    CHECK(b.ensure(s, 100, 4096, 0, true) == hipErrorOutOfMemory && !b.p && b.cap == 0);
+    CHECK(b.ensure(s, 100, 4096, 0, true) == hipSuccess && b.p && b.cap == 4096);
+    F.fail['Z'] = 1;  // the memset of a grown buffer: nothing is kept
+    CHECK(b.ensure(s, 8192, 4096, 0, true) == hipErrorInvalidValue && !b.p && b.cap == 0);
+    CHECK(F.dev.empty());
+    CHECK(b.ensure(s, 8192, 4096, 0, true) == hipSuccess && b.cap == 8192);
+    F.fail['M'] = 1;  // the allocation after the old one was freed
+    CHECK(b.ensure(s, 10000, 4096, 0, true) == hipErrorOutOfMemory && !b.p && b.cap == 0);
+    CHECK(F.dev.empty());
+    CHECK(b.ensure(s, 10000, 4096, 0, true) == hipSuccess && b.cap == 10000);
+    F.fail['S'] = 1;  // the drain: the old buffer stays, whole
+    void *old = b.p;
+    CHECK(b.ensure(s, 20000, 4096, 0, true) == hipErrorUnknown && b.p == old && b.cap == 10000);
+    CHECK(b.ensure(s, 20000, 4096, 0, true) == hipSuccess && b.cap == 20000);
+  }
+  CHECK(F.dev.empty() && F.mallocs == F.frees);
+  {
+    PinnedBlock e;
+    F.fail['H'] = 1;
+    CHECK(e.ensure() == hipErrorOutOfMemory && !e.h && !e.d);
+    F.fail['P'] = 1;  // the device-pointer lookup: the host block is given back
+    CHECK(e.ensure() == hipErrorInvalidValue && !e.h && !e.d && F.pin.empty());
+    CHECK(e.ensure() == hipSuccess && e.h && e.d);
+    CHECK(F.last_host_flags == hipHostMallocCoherent);
+    for (int i = 0; i < 64; ++i) CHECK(static_cast<uint8_t *>(e.h)[i] == 0);
+    const std::string l = F.log;
+    CHECK(e.ensure() == hipSuccess && F.log == l);  // made once
+    PinnedBlock f(std::move(e));
+    CHECK(!e.h && !e.d && f.h && f.d);
+  }
+  CHECK(F.pin.empty() && F.host_mallocs == F.host_frees && F.host_mallocs == 2);
+}
+
+struct Slot {
+  StreamBuf a, b;
+  PinnedBlock pin;
+  int tag = 0;
+};
+
+static void test_registry() {
+  F = Fake{};
+  const hipStream_t s = stream(3), s2 = stream(4);
+  {
+    StreamRegistry<Slot> reg;
+    CHECK(reg.find(0, s) == nullptr);
+    Slot *x = reg.find_or_make(0, s);
+    CHECK(x && reg.find_or_make(0, s) == x && reg.find(0, s) == x && reg.size() == 1);
+    // the same handle on another device, another stream on the same device
+    Slot *y = reg.find_or_make(1, s);
+    Slot *z = reg.find_or_make(0, s2);
+    CHECK(y != x && z != x && z != y && reg.size() == 3);
+    CHECK(x->a.ensure(s, 100, 4096, 0, true) == hipSuccess && x->pin.ensure() == hipSuccess);
+    CHECK(y->a.ensure(s, 100, 4096, 0, true) == hipSuccess && y->pin.ensure() == hipSuccess);
+    CHECK(y->b.ensure(s, 9000, 4096, 0, false) == hipSuccess);
+    x->tag = 7;
+    void *xa = x->a.p, *ya = y->a.p, *yb = y->b.p, *yh = y->pin.h;
+    // 100 more slots: the first ones and their buffers stay where they are
+    for (uintptr_t i = 0; i < 100; ++i) {
+      Slot *n = reg.find_or_make(int(i % 3), stream(100 + i));
+      CHECK(n->a.ensure(stream(100 + i), 64, 64, 0, false) == hipSuccess);
+    }
+    CHECK(reg.size() == 103 && reg.find(0, s) == x && reg.find(1, s) == y);
+    CHECK(x->tag == 7 && x->a.p == xa && x->a.cap == 4096 && y->a.p == ya);
+    memset(xa, 1, 4096);  // still ours
+    // release on device 0 leaves device 1's slot and allocations alone
+    const int frees = F.frees, host_frees = F.host_frees;
+    reg.release(0, s);
+    CHECK(F.frees == frees + 1 && F.host_frees == host_frees + 1 && !F.dev.count(xa));
+    CHECK(reg.find(0, s) == nullptr && reg.find(1, s) == y && reg.size() == 102);
+    CHECK(y->a.p == ya && y->b.p == yb && y->pin.h == yh);
+    CHECK(F.dev.count(ya) && F.dev.count(yb) && F.pin.count(yh));
+    memset(yb, 2, 9000);
+    reg.release(0, s);  // no such slot: nothing happens
+    reg.release(2, s);
+    CHECK(reg.size() == 102 && F.frees == frees + 1);
+    // a released key makes a fresh, empty slot
+    Slot *x2 = reg.find_or_make(0, s);
+    CHECK(x2->tag == 0 && !x2->a.p && !x2->pin.h);
+    // release everything
+    reg.release(0, s);
+    reg.release(1, s);
+    reg.release(0, s2);
+    for (uintptr_t i = 0; i < 100; ++i) reg.release(int(i % 3), stream(100 + i));
+    CHECK(reg.size() == 0);
+    CHECK(F.dev.empty() && F.pin.empty());
+    CHECK(F.mallocs == F.frees && F.mallocs == 103);
+    CHECK(F.host_mallocs == F.host_frees && F.host_mallocs == 2);
+    // what is left at the registry's end goes with it
+    CHECK(reg.find_or_make(0, s)->a.ensure(s, 1, 64, 0, false) == hipSuccess);
+  }
+  CHECK(F.dev.empty() && F.mallocs == F.frees);
+}
+
+static void test_stream_device() {
+  F = Fake{};
+  const hipStream_t s = stream(5);
+  F.stream_dev[s] = 1;
+  {
+    StreamDevice sd(s);  // a stream of device 1 while device 0 is current
+    CHECK(sd.e == hipSuccess && sd.dev == 1 && sd.prev == 0 && F.cur == 1);
+  }
+  CHECK(F.cur == 0 && F.set_device_log == "10");
+  {
+    StreamDevice sd(nullptr);  // the null stream: the current device
+    CHECK(sd.dev == 0 && F.cur == 0);
+  }
+  F.cur = 1;
+  {
+    StreamDevice sd(s);
+    CHECK(sd.dev == 1);
+  }
+  CHECK(F.cur == 1 && F.set_device_log == "10");  // nothing to switch
+}
+
+static void test_pass_plan() {
+  const uint64_t ns[] = {1, 2, 63, 64, 65, 511, 512, 513, 2048, 65536};
+  const uint64_t lens[] = {0, 1, 1 << 10, (1 << 10) + 1, 64 << 10, 1 << 20, 2 << 20,
+                           16 << 20, (16 << 20) + 1, 32 << 20, 4ull << 30};
+  const uint32_t targets[] = {0, 2048};
+  for (uint64_t n : ns)
+    for (uint64_t len : lens)
+      for (uint32_t target : targets) {
+        const PassPlan p = pass_plan(n, len, target, 512);
+        const uint64_t C = len ? (len + 1023) >> 10 : 1;
+        CHECK(p.g >= 1 && p.g <= 64 && (p.g & (p.g - 1)) == 0);
+        CHECK(((256ull * p.g) << p.sl) >= C);  // every chunk has a lane
+        if (target == 0)  // no split: the fewest workgroups that cover it
+          CHECK(p.sl == 0 || ((256ull * p.g) << (p.sl - 1)) < C);
+        if (C <= 256ull * 256 * 64) CHECK(p.sl <= kMaxSplitLog2);
+      }
+  // spot values at the defaults (split target 2048, latency bound 512)
+  struct {
+    uint64_t n, len;
+    uint32_t target;
+    int g;
+    uint32_t sl;
+  } spots[] = {{65536, 1 << 20, 2048, 4, 0}, {1, 1 << 20, 2048, 1, 2},
+               {64, 2 << 20, 2048, 2, 2},    {512, 1 << 20, 2048, 1, 2},
+               {1, 32 << 20, 2048, 1, 7},    {1, 1 << 20, 0, 4, 0}};
+  for (const auto &c : spots) {
+    const PassPlan p = pass_plan(c.n, c.len, c.target, 512);
+    CHECK(p.g == c.g && p.sl == c.sl);
+  }
+  CHECK(quad_qpw(4 << 20) == 64 && quad_qpw((4 << 20) + 1) == 256);
+}
+
+int main() {
+  test_ensure();
+  test_failures();
+  test_registry();
+  test_stream_device();
+  test_pass_plan();
+  if (g_failed) {
+    fprintf(stderr, "stream_scratch_test: %d checks failed\n", g_failed);
+    return 1;
+  }
+  printf("stream_scratch_test: ok\n");
+  return 0;
+}

@@ -270,6 +270,67 @@ def test_reuse(gpu, O):
         _check(torch, refs, ct, offs, _want(O, name, None), total)
 
 
+def _open_no_plaintext(N, O, torch, name, bs, n, stream):
+    """A verified read of n blocks of bs bytes on the composed route, salted,
+    no plaintext buffer, block 1 damaged and the last ref's DEK foreign: the
+    status words, and what the oracle's refs say they are."""
+    if name not in _cache:
+        data = O.fill_splitmix(n * bs, 31 + n * bs)
+        posts = [O.post(SALT, data[o:o + bs], None) for o in range(0, n * bs, bs)]
+        ct = bytearray(b"".join(c for _, c in posts))
+        refs = bytearray(b"".join(r for r, _ in posts))
+        ct[bs + 5] ^= 1
+        refs[64 * (n - 1) + 33] ^= 1
+        _cache[name] = (bytes(ct), bytes(refs))
+    ct, refs = _cache[name]
+    d_ct = torch.from_numpy(np.frombuffer(ct, dtype=np.uint8).copy()).cuda()
+    d_refs = torch.from_numpy(np.frombuffer(refs, dtype=np.uint8).copy()).cuda()
+    d_st = torch.full((n,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    N.check(N.lib.glfsx_open_batch_device(SALT, None, d_ct.data_ptr(), n * bs, bs,
+                                          d_refs.data_ptr(), None, d_st.data_ptr(),
+                                          stream.cuda_stream))
+    torch.cuda.synchronize()
+    want = [0] * n
+    want[1], want[n - 1] = 3, 2  # CID and DEK of block 1; the DEK of the last
+    return [int(x) & 0xFFFFFFFF for x in d_st.cpu().tolist()], want
+
+
+def test_scratch_small_large_small(gpu, O):
+    """The two routes whose per-stream scratch outgrows its 1 MiB floor at
+    small sizes, on a stream of their own (so its buffers start empty): a
+    small call, a large one that makes the buffer grow, the small one again.
+    Ragged post: 64 messages of about 1 MiB in all, then 48 MiB (more than
+    32768 chunks at 32 B of CV scratch each).  Verified read, composed route,
+    no plaintext buffer (the scratch holds the plaintext): 8 x 64 KiB, then
+    8 x 1 MiB.  Every ref and status word is the oracle's, and the third
+    result is the first byte for byte."""
+    import torch
+    N = gpu
+    s = torch.cuda.Stream()
+    small = [(i * 997) % (32 * KIB) + 1 for i in range(64)]
+    large = ([5 * MIB + 77] * 4 + [3 * MIB + 1025] * 5 + [2 * MIB] * 4 + [MIB + 1] * 4 +
+             [100 * KIB + 3] * 8 + [0, 1, 1023, 1025, 65537])
+    random.Random(15).shuffle(large)
+    assert abs(sum(small) - MIB) < MIB // 8
+    assert sum((ln + 1023) // 1024 for ln in large) > 32768
+    got = []
+    for name, lens, seed in (("grow_s", small, 29), ("grow_l", large, 30), ("grow_s", small, 29)):
+        offs, total = _offsets(lens, 16, 0, gap=3)
+        got.append(_run(N, O, name, lens, seed, offs, total, stream=s))
+    assert got[0] == got[2]
+    prev = N.set_open_route(1)
+    try:
+        got = []
+        for name, bs in (("open_s", 64 * KIB), ("open_l", MIB), ("open_s", 64 * KIB)):
+            st, want = _open_no_plaintext(N, O, torch, name, bs, 8, s)
+            assert st == want, (name, st)
+            got.append(st)
+        assert got[0] == got[2]
+    finally:
+        N.set_open_route(prev)
+
+
 ROUTE_LENS = [0, 100, 4096, 16384, 16385, 40000, 65536, 300000, 2 * MIB, 2 * MIB + 1, 5 * MIB]
 
 

@@ -1,7 +1,10 @@
-"""The host runtime's HIP-free units -- DevicePool and the job builders of
-glfs_amd/csrc/host.h -- as a stand-alone program (tests/c/host_units_test.cpp)
-built with the host compiler under AddressSanitizer and UBSan.  It runs as
-its own process: nothing is loaded into Python and no GPU call is made."""
+"""The units that need no GPU, as stand-alone programs built with the host
+compiler under AddressSanitizer and UBSan: the host runtime's DevicePool and
+job builders (glfs_amd/csrc/host.h, tests/c/host_units_test.cpp), and the
+launch layer's per-stream scratch and launch plans (stream_scratch.h,
+launch_plan.h; tests/c/stream_scratch_test.cpp, over a fake HIP runtime of
+its own).  Each runs as its own process: nothing is loaded into Python and no
+GPU call is made."""
 import os
 import shutil
 import subprocess
@@ -11,19 +14,27 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_pool_and_job_builders_under_sanitizers(tmp_path):
+def _build_and_run(tmp_path, name):
     cxx = shutil.which("g++") or shutil.which("c++")
     if not cxx:
         pytest.fail("no host C++ compiler")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")  # host.h's types come with the HIP headers
-    out = str(tmp_path / "host_units_test")
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")  # hipError_t, hipStream_t: the HIP headers
+    out = str(tmp_path / name)
     subprocess.check_call(
         [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
          "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
          "-isystem", os.path.join(rocm, "include"),
          "-I", os.path.join(ROOT, "glfs_amd", "csrc"),
-         os.path.join(ROOT, "tests", "c", "host_units_test.cpp"), "-o", out])
+         os.path.join(ROOT, "tests", "c", name + ".cpp"), "-o", out])
     p = subprocess.run([out], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stdout + p.stderr
-    assert "host_units_test: ok" in p.stdout
+    assert name + ": ok" in p.stdout
     assert p.stderr == "", p.stderr  # the sanitizers report nothing
+
+
+def test_pool_and_job_builders_under_sanitizers(tmp_path):
+    _build_and_run(tmp_path, "host_units_test")
+
+
+def test_stream_scratch_and_launch_plan_under_sanitizers(tmp_path):
+    _build_and_run(tmp_path, "stream_scratch_test")
