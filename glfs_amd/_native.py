@@ -126,6 +126,10 @@ SIGNATURES = {
     "glfsx_open_batch_device": (_INT, [_CP, _CP, _VP, _U64, _U64, _VP, _VP, _VP, _VP]),
     "glfsx_open_batch": (_INT, [_CP, _CP, _VP, _U64, _U64, _VP, _VP, _VP,
                                 ctypes.POINTER(ctypes.c_uint64)]),
+    "glfsx_open_ragged_device": (_INT, [_CP, _CP, _VP, _VP, _VP, _U64, _U64, _VP, _VP, _VP,
+                                        _VP]),
+    "glfsx_open_blobs": (_INT, [_CP, _CP, _VP, _VP, _VP, _U64, _VP, _VP, _VP,
+                                ctypes.POINTER(ctypes.c_uint64)]),
     "glfsx_set_open_route": (_INT, [_INT]),
     "glfsx_sink_count": (_INT, [_VP, _INT, _VP, _VP, _U64]),
     "glfsx_tree_encode": (_INT, [_U64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U64,

@@ -909,6 +909,41 @@ def open_level(ctexts, refs, block_size: int, salt: Optional[bytes],
     return outs if want_ptext else []
 
 
+def open_blobs(ctexts, refs, salt: Optional[bytes], cid_key: Optional[bytes] = None,
+               want_ptext: bool = True):
+    """open_level's checks over blobs of any mix of lengths (each at most
+    16 MiB, the empty one included) in ONE glfsx_open_blobs call: salt is the
+    level's salt as post took it (None: no DEK check), the same for every
+    blob.  Returns (ptexts, statuses): the plaintexts in order (an empty list
+    when want_ptext is false) and a status word per blob -- GLFSX_BAD_CID |
+    GLFSX_BAD_DEK, 0 for a good one.  Never raises for a bad blob; the
+    plaintext of a bad blob is not to be used."""
+    n = len(ctexts)
+    if n == 0:
+        return [], []
+    lens = [len(c) for c in ctexts]
+    offs, pos = [], 0
+    for ln in lens:
+        offs.append(pos)
+        pos += ln
+    data = b"".join(bytes(c) for c in ctexts)
+    rb = b"".join(r.marshal_binary() for r in refs)
+    if len(rb) != REF_SIZE * n:
+        raise ValueError("open_blobs needs one ref per ctext")
+    out = ctypes.create_string_buffer(max(pos, 1)) if want_ptext else None
+    st = (ctypes.c_uint32 * n)()
+    rc = N.lib.glfsx_open_blobs(_salt_arg(salt), cid_key, data or b"\0",
+                                (ctypes.c_uint64 * n)(*offs), (ctypes.c_uint64 * n)(*lens), n,
+                                rb, out, st, None)
+    if rc != N.GLFSX_E_CORRUPT:
+        N.check(rc)
+    ptexts = []
+    if want_ptext:
+        raw = out.raw
+        ptexts = [raw[o:o + ln] for o, ln in zip(offs, lens)]
+    return ptexts, list(st)
+
+
 def _tree_levels(get, root: Root, salt: Optional[bytes] = None,
                  cid_key: Optional[bytes] = None, *, _check: bool = False,
                  _keep: Optional[dict] = None) -> list:

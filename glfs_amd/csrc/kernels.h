@@ -2,8 +2,9 @@
 // units: runtime, oneshot, copy_pool, writer, create, blobs, read) and the
 // gfx950 kernels: post_kernels.hip (the launches, with its fragments b3_arx.h,
 // pass_kernels.h, quad_kernels.h, one_kernels.h, small_kernels.h,
-// ragged_kernels.h, read_kernels.h and open_kernels.h holding the kernels by
-// family; launch_plan.h the shape of a bulk launch and stream_scratch.h the
+// ragged_kernels.h, read_kernels.h, open_kernels.h and ragged_open_kernels.h
+// holding the kernels by family; ragged_groups.h the host form's grouping,
+// launch_plan.h the shape of a bulk launch and stream_scratch.h the
 // per-stream scratch its host half keeps, both free of device code),
 // tree_kernels.hip and
 // xof_kernels.hip (device_common.h: definitions the three share).  Not part
@@ -200,6 +201,27 @@ struct OpenJob {
 };
 hipError_t launch_open(const OpenJob &, hipStream_t);
 int set_open_route(int route);
+
+// The same checks over messages of unequal length in throughput form
+// (ragged_open_kernels.h): message i is ctext[offs[i] .. offs[i]+lens[i]), its
+// ref at refs + 64*i, its plaintext goes to ptext at the same offset and its
+// status word (as OpenJob's) to status[i].  The ragged post's plan and
+// structure: work follows the bytes, at most five launches whatever n and one
+// host wait, for the plan's totals.  A message of more than max_len bytes
+// (max_len <= kMaxRaggedLen) is neither read nor written and gets status 1.
+// With ptext == ctext the messages must be disjoint.
+struct OpenRaggedJob {
+  const uint8_t *ctext;
+  uint8_t *ptext;               // nullable; same offsets as ctext; may be ctext
+  const uint64_t *offs, *lens;  // device arrays
+  uint64_t n, max_len;
+  const uint8_t *refs;          // 64 B per message, 4-B aligned
+  uint32_t *status;             // 4-B aligned
+  uint32_t salt[8];
+  uint32_t cid_key[8];          // the IV when unkeyed
+  bool salted, cid_keyed;
+};
+hipError_t launch_open_ragged(const OpenRaggedJob &, hipStream_t);
 
 // Synthetic splitmix64 byte stream (see oracle_fill_splitmix); offset % 8 == 0.
 hipError_t launch_fill(uint8_t *dst, uint64_t offset, uint64_t n, uint64_t seed,

@@ -52,6 +52,7 @@ namespace {
 #include "ragged_kernels.h"
 #include "read_kernels.h"
 #include "open_kernels.h"
+#include "ragged_open_kernels.h"
 
 // The host side: launch plans and launches.
 
@@ -132,6 +133,9 @@ struct ScratchSlot {
   StreamBuf rcv;       // ragged post: chunk and group CVs (RArgs::cvs, gcv)
   PinnedBlock rtot;    // ragged post: the plan's three totals
   StreamBuf open;      // verified read, composed route: digests, plaintext
+  StreamBuf oplan;     // ragged open: the plan's prefixes (RArgs::pre, wpre)
+  StreamBuf ocv;       // ragged open: chunk and group CVs, 64 B each
+  PinnedBlock otot;    // ragged open: the plan's three totals
 };
 // g_scratch_mu guards the registry and every slot, and is held across a
 // getter's whole body, the drain of a growing buffer included: narrowing it
@@ -668,7 +672,8 @@ hipError_t launch_post_ragged(const RaggedJob &job, hipStream_t s) {
   if (e != hipSuccess) return e;
   a.pre = reinterpret_cast<uint64_t *>(d_plan);
   a.wpre = a.pre + job.n;
-  hipLaunchKernelGGL(k_rag_count, dim3(uint32_t(a.m)), dim3(kRagWG), 0, s, a);
+  hipLaunchKernelGGL(k_rag_count<false>, dim3(uint32_t(a.m)), dim3(kRagWG), 0, s, a,
+                     static_cast<uint32_t *>(nullptr), 0u);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_rag_prefix<1024>, dim3(3), dim3(1024), 0, s, a.wpre, a.m, d_tot);
@@ -944,6 +949,105 @@ hipError_t launch_open(const OpenJob &job, hipStream_t s) {
   const uint64_t C = (job.bs + 1023) >> 10;
   const int g = C <= 256 ? 1 : C <= 512 ? 2 : C <= 1024 ? 4 : 8;
   return with_g<1, 2, 4, 8>(g, [&](auto G) { return launch_open_g<G()>(a, aligned, s); });
+}
+
+// ---- The ragged open (ragged_open_kernels.h) ----
+
+// The ragged open's buffers on stream s, in rag_get's form.
+static hipError_t rag_open_get(hipStream_t s, size_t plan, size_t cv, uint8_t **d_plan,
+                               uint8_t **d_cv, uint64_t **tot, uint64_t **d_tot) {
+  SlotLock g(s);
+  if (g.sd.e != hipSuccess) return g.sd.e;
+  hipError_t e = g.sl->otot.ensure();
+  if (e != hipSuccess) return e;
+  e = g.sl->oplan.ensure(s, plan, kGrowFloor, 4, false);
+  if (e != hipSuccess) return e;
+  e = g.sl->ocv.ensure(s, cv, kGrowFloor, 4, false);
+  if (e != hipSuccess) return e;
+  *d_plan = g.sl->oplan.as<uint8_t>();
+  *d_cv = g.sl->ocv.as<uint8_t>();
+  *tot = static_cast<uint64_t *>(g.sl->otot.h);
+  *d_tot = static_cast<uint64_t *>(g.sl->otot.d);
+  return hipSuccess;
+}
+
+// The chunk pass and the merge levels that have work, in mode MODE.
+template <int MODE>
+static hipError_t launch_rag_open_pass(ROArgs a, const uint64_t tot[3], hipStream_t s) {
+  a.r.total = tot[0];
+  const uint64_t tiles = (tot[0] + 255) >> 8;
+  const dim3 grid(uint32_t(std::min<uint64_t>(tiles, 1u << 20))), block(256);
+  // few tiles: the compiler's ARX form, as launch_rag_chunk
+  if (tiles <= latency_wgs())
+    hipLaunchKernelGGL((k_rag_open_chunk<MODE, 0>), grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL((k_rag_open_chunk<MODE, 2>), grid, block, 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (tot[1]) {
+    a.r.total = tot[1];
+    hipLaunchKernelGGL(k_rag_open_merge_a<MODE == 2>,
+                       dim3(uint32_t(std::min<uint64_t>(tot[1], 1u << 20))), dim3(256), 0, s, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (tot[2]) {
+    a.r.total = tot[2];
+    hipLaunchKernelGGL(k_rag_open_merge_b<MODE == 2>,
+                       dim3(uint32_t(std::min<uint64_t>(tot[2], 1u << 20))), dim3(256), 0, s, a);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
+hipError_t launch_open_ragged(const OpenRaggedJob &job, hipStream_t s) {
+  if (job.n == 0) return hipSuccess;
+  if (job.max_len > kMaxRaggedLen) return hipErrorInvalidValue;
+  ROArgs a{};
+  a.r.src = job.ctext;
+  a.r.ctext = job.ptext;
+  a.r.offs = job.offs;
+  a.r.lens = job.lens;
+  a.r.n = job.n;
+  a.r.lo = kRaggedAll;
+  a.r.hi = job.max_len;
+  a.r.refs = const_cast<uint8_t *>(job.refs);
+  a.r.m = (job.n + kRagWG - 1) / kRagWG;
+  a.status = job.status;
+  uint8_t *d_plan, *d_cv;
+  uint64_t *tot, *d_tot;
+  hipError_t e = rag_open_get(s, 8 * (job.n + 3 * (a.r.m + 1)), 0, &d_plan, &d_cv, &tot, &d_tot);
+  if (e != hipSuccess) return e;
+  a.r.pre = reinterpret_cast<uint64_t *>(d_plan);
+  a.r.wpre = a.r.pre + job.n;
+  // a message above max_len is neither read nor written: it fails closed
+  hipLaunchKernelGGL(k_rag_count<true>, dim3(uint32_t(a.r.m)), dim3(kRagWG), 0, s, a.r,
+                     job.status, 1u /* GLFSX_BAD_CID */);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_rag_prefix<1024>, dim3(3), dim3(1024), 0, s, a.r.wpre, a.r.m, d_tot);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // the one host wait of the call: the totals size the CV scratch and the
+  // launches below
+  e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return e;
+  const uint64_t totals[3] = {__atomic_load_n(tot + 0, __ATOMIC_RELAXED),
+                              __atomic_load_n(tot + 1, __ATOMIC_RELAXED),
+                              __atomic_load_n(tot + 2, __ATOMIC_RELAXED)};
+  if (totals[0] == 0) return hipSuccess;  // nothing selected
+  e = rag_open_get(s, 0, 64 * (totals[0] + totals[1]), &d_plan, &d_cv, &tot, &d_tot);
+  if (e != hipSuccess) return e;
+  a.r.cvs = reinterpret_cast<uint32_t *>(d_cv);
+  a.r.gcv = a.r.cvs + 16 * totals[0];
+  for (int i = 0; i < 8; ++i) {
+    a.r.key[i] = job.cid_key[i];
+    a.salt[i] = job.salt[i];
+  }
+  a.r.base = job.cid_keyed ? kKeyed : 0u;
+  if (job.salted) return launch_rag_open_pass<2>(a, totals, s);
+  if (job.ptext) return launch_rag_open_pass<1>(a, totals, s);
+  return launch_rag_open_pass<0>(a, totals, s);
 }
 
 }  // namespace glfsx

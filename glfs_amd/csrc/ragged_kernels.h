@@ -85,8 +85,11 @@ __device__ __forceinline__ uint64_t rag_base(const RArgs &a, uint64_t i) {
 }
 
 // Plan, first level: the packed counts of 256 messages, their exclusive
-// prefix inside the workgroup, and the workgroup's three totals.
-__global__ __launch_bounds__(kRagWG) void k_rag_count(RArgs a) {
+// prefix inside the workgroup, and the workgroup's three totals.  MARK (the
+// ragged open, ragged_open_kernels.h): a message that is not selected gets
+// the word `mark` at unsel[i] -- it fails closed without being read.
+template <bool MARK>
+__global__ __launch_bounds__(kRagWG) void k_rag_count(RArgs a, uint32_t *unsel, uint32_t mark) {
   __shared__ uint64_t s[kRagWG];
   const uint32_t t = threadIdx.x;
   const uint64_t i = uint64_t(blockIdx.x) * kRagWG + t;
@@ -96,6 +99,8 @@ __global__ __launch_bounds__(kRagWG) void k_rag_count(RArgs a) {
     if (rag_selected(len, a.lo, a.hi)) {
       const uint64_t c = rag_chunks(len);
       x = c | ((c > 1 ? (c + 255) >> 8 : 0ull) << 32) | (uint64_t(c > 256) << 48);
+    } else if constexpr (MARK) {
+      unsel[i] = mark;
     }
   }
   uint64_t v = x;

@@ -1,6 +1,7 @@
 // read.cpp -- the read side: batched decrypt and verified read ("open") from
 // device or host memory.
 #include "host.h"
+#include "ragged_groups.h"
 
 using namespace glfsx;
 using namespace glfsx::host;
@@ -117,7 +118,8 @@ int slab_pipeline(Ctx *c, const void *ctext, uint64_t total, uint64_t block_size
   return 0;
 }
 
-void open_keys(OpenJob &j, const uint8_t *salt, const uint8_t *cid_key) {
+template <class J>  // OpenJob, OpenRaggedJob
+void open_keys(J &j, const uint8_t *salt, const uint8_t *cid_key) {
   j.salted = salt != nullptr;
   if (salt) words_from_key(j.salt, salt);
   set_cid_key(j, cid_key);
@@ -210,5 +212,145 @@ int glfsx_open_batch(const uint8_t *salt, const uint8_t *cid_key, const void *ct
 }
 
 int glfsx_set_open_route(int route) { return set_open_route(route); }
+
+int glfsx_open_ragged_device(const uint8_t *salt, const uint8_t *cid_key,
+                             const void *d_ctext, const uint64_t *d_offsets,
+                             const uint64_t *d_lengths, uint64_t n, uint64_t max_len,
+                             const void *d_refs, void *d_ptext, uint32_t *d_status,
+                             void *stream) {
+  if (!d_ctext || !d_refs || !d_status) return fail(GLFSX_E_ARG, "null argument");
+  if ((reinterpret_cast<uintptr_t>(d_refs) | reinterpret_cast<uintptr_t>(d_status)) & 3)
+    return fail(GLFSX_E_ARG, "refs and status must be 4-byte aligned");
+  if (max_len > kMaxRaggedLen)
+    return fail(GLFSX_E_UNSUPPORTED, "max_len %llu above the ragged open's %llu",
+                (unsigned long long)max_len, (unsigned long long)kMaxRaggedLen);
+  if (n == 0) return 0;
+  if (!d_offsets || !d_lengths) return fail(GLFSX_E_ARG, "null argument");
+  Ctx *c;
+  if (int e = ctx_get(&c)) return e;
+  OpenRaggedJob job{};
+  open_keys(job, salt, cid_key);
+  job.ctext = static_cast<const uint8_t *>(d_ctext);
+  job.ptext = static_cast<uint8_t *>(d_ptext);
+  job.offs = d_offsets;
+  job.lens = d_lengths;
+  job.n = n;
+  job.max_len = max_len;
+  job.refs = static_cast<const uint8_t *>(d_refs);
+  job.status = d_status;
+  HIP_TRY(launch_open_ragged(job, pick_stream(c, stream)));
+  return 0;
+}
+
+int glfsx_open_blobs(const uint8_t *salt, const uint8_t *cid_key, const void *ctext,
+                     const uint64_t *offsets, const uint64_t *lengths, uint64_t n,
+                     const uint8_t *refs, void *ptext, uint32_t *status_out,
+                     uint64_t *n_bad) {
+  if (n_bad) *n_bad = 0;
+  if (n == 0) return 0;
+  if (!ctext || !refs || !offsets || !lengths) return fail(GLFSX_E_ARG, "null argument");
+  uint64_t max_len = 0;
+  for (uint64_t i = 0; i < n; ++i) max_len = std::max(max_len, lengths[i]);
+  if (max_len > kMaxRaggedLen)
+    return fail(GLFSX_E_UNSUPPORTED, "a message of %llu bytes is above the ragged open's %llu",
+                (unsigned long long)max_len, (unsigned long long)kMaxRaggedLen);
+  std::vector<RaggedGroup> groups;
+  std::vector<uint64_t> soff;
+  ragged_groups(lengths, n, kRaggedGroupBytes, &groups, &soff);
+  Ctx *c;
+  if (int e = ctx_get(&c)) return e;
+  OpenRaggedJob keys{};
+  open_keys(keys, salt, cid_key);
+  const uint8_t *src = static_cast<const uint8_t *>(ctext);
+  uint8_t *dst = static_cast<uint8_t *>(ptext);
+  // The groups one after the other through the thread's first pooled slot:
+  // gathered into its pinned staging by the copy threads, opened in place on
+  // the device, the plaintext scattered back from the pinned staging.
+  Ctx::BlobSlot &g = c->bslot[0];
+  uint64_t bad = 0, first_bad = 0;
+  uint32_t first_status = 0;
+  auto run = [&](const RaggedGroup &grp) -> int {
+    const uint64_t m = grp.i1 - grp.i0;
+    if (int e = g.h_in.ensure(grp.bytes + 64)) return e;
+    if (int e = g.d_in.ensure(grp.bytes + 64)) return e;
+    if (int e = g.h_meta.ensure(20 * m)) return e;  // offsets, lengths, then status
+    if (int e = g.d_meta.ensure(20 * m)) return e;
+    if (int e = g.h_refs.ensure(64 * m)) return e;
+    if (int e = g.d_refs.ensure(64 * m)) return e;
+    uint64_t *lo = reinterpret_cast<uint64_t *>(g.h_meta.p), *ll = lo + m;
+    // gather, copying each run of messages contiguous on both sides at once
+    uint64_t run_src = 0, run_dst = 0, run_len = 0;
+    for (uint64_t j = 0; j < m; ++j) {
+      const uint64_t i = grp.i0 + j, len = lengths[i];
+      lo[j] = soff[i];
+      ll[j] = len;
+      if (len == 0) continue;
+      if (run_len && offsets[i] == run_src + run_len && soff[i] == run_dst + run_len) {
+        run_len += len;
+      } else {
+        if (run_len) par_memcpy(g.h_in.u8() + run_dst, src + run_src, run_len);
+        run_src = offsets[i];
+        run_dst = soff[i];
+        run_len = len;
+      }
+    }
+    if (run_len) par_memcpy(g.h_in.u8() + run_dst, src + run_src, run_len);
+    memcpy(g.h_refs.p, refs + 64 * grp.i0, 64 * m);
+    if (grp.bytes)
+      HIP_TRY(hipMemcpyAsync(g.d_in.p, g.h_in.p, grp.bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(g.d_meta.p, g.h_meta.p, 16 * m, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(g.d_refs.p, g.h_refs.p, 64 * m, hipMemcpyHostToDevice, c->stream));
+    OpenRaggedJob job = keys;
+    job.ctext = g.d_in.u8();
+    job.ptext = ptext ? g.d_in.u8() : nullptr;  // in place: staged messages are disjoint
+    job.offs = reinterpret_cast<const uint64_t *>(g.d_meta.p);
+    job.lens = job.offs + m;
+    job.n = m;
+    job.max_len = max_len;
+    job.refs = g.d_refs.u8();
+    job.status = reinterpret_cast<uint32_t *>(g.d_meta.u8() + 16 * m);
+    HIP_TRY(launch_open_ragged(job, c->stream));
+    if (ptext && grp.bytes)
+      HIP_TRY(hipMemcpyAsync(g.h_in.p, g.d_in.p, grp.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(g.h_meta.u8() + 16 * m, job.status, 4 * m, hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(stream_wait(c->stream));
+    const uint32_t *st = reinterpret_cast<const uint32_t *>(g.h_meta.u8() + 16 * m);
+    if (status_out) memcpy(status_out + grp.i0, st, 4 * m);
+    for (uint64_t j = 0; j < m; ++j)
+      if (st[j] && bad++ == 0) {
+        first_bad = grp.i0 + j;
+        first_status = st[j];
+      }
+    if (ptext) {  // scatter, by the same runs
+      run_len = 0;
+      for (uint64_t j = 0; j < m; ++j) {
+        const uint64_t i = grp.i0 + j, len = lengths[i];
+        if (len == 0) continue;
+        if (run_len && offsets[i] == run_src + run_len && soff[i] == run_dst + run_len) {
+          run_len += len;
+        } else {
+          if (run_len) par_memcpy(dst + run_src, g.h_in.u8() + run_dst, run_len);
+          run_src = offsets[i];
+          run_dst = soff[i];
+          run_len = len;
+        }
+      }
+      if (run_len) par_memcpy(dst + run_src, g.h_in.u8() + run_dst, run_len);
+    }
+    return 0;
+  };
+  for (const RaggedGroup &grp : groups)
+    if (int e = run(grp)) {
+      (void)hipStreamSynchronize(c->stream);  // nothing may still use the staging
+      return e;
+    }
+  if (n_bad) *n_bad = bad;
+  if (bad == 0) return 0;
+  return fail(GLFSX_E_CORRUPT, "message %llu of %llu failed its %s check%s (%llu bad in all)",
+              (unsigned long long)first_bad, (unsigned long long)n,
+              first_status == 3 ? "CID and DEK" : first_status == 1 ? "CID" : "DEK",
+              first_status == 3 ? "s" : "", (unsigned long long)bad);
+}
 
 }  // extern "C"

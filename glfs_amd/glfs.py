@@ -65,6 +65,18 @@ class TypedWriter:
         return Ref(self.ty, root)
 
 
+def _blob_count(root: Root) -> int:
+    """The store blobs of a non-empty bigblob: its data blocks and the index
+    nodes of every level above them (blob.go:152-206)."""
+    n = -(-root.size // root.block_size)
+    bf = bigblob.branching_factor(root.block_size)
+    total = n
+    while n > 1:
+        n = -(-n // bf)
+        total += n
+    return total
+
+
 class Machine:
     """machine.go:27-48."""
 
@@ -172,6 +184,86 @@ class Machine:
         from.  Returns the number of blobs checked; raises
         bigblob.ErrCorrupt."""
         return self.bbag.verify(store, ref.root, salt=self.make_salt(ref.type))
+
+    VERIFY_BATCH_BYTES = 64 << 20   # one-block objects checked per open_blobs call
+    MAX_OPEN_BLOB = 16 << 20        # glfsx_open_blobs' longest message
+
+    def verify_tree(self, store, ref: Ref, cid_key: Optional[bytes] = None) -> int:
+        """fsck of everything ref reaches: verify of ref's own object and, for
+        a tree, of every entry below it, breadth-first.  At each depth the
+        objects of one block (0 < size <= min(block_size, 16 MiB)) are checked
+        by type under DeriveKey(typeSalt, "raw") through bigblob.open_blobs,
+        in batches of at most 64 MiB -- plaintext is taken for trees only,
+        whose entries are the next depth; objects of several blocks go
+        through bigblob.Machine.verify (a tree's bytes then through the
+        verified read_all), empty ones through the empty-blob check.  An
+        object reached twice is checked once.  Returns the number of store
+        blobs checked; raises bigblob.ErrCorrupt for the first bad blob in
+        walk order, its `path` the entry's path ("" for ref itself)."""
+        from .tree import read_tree_bytes
+        seen, checked = set(), 0
+        frontier = [("", ref)]
+        while frontier:
+            objs = []
+            for path, r in frontier:
+                k = (r.type, r.root.ref.cid, r.root.ref.dek, r.root.size, r.root.block_size)
+                if k not in seen:
+                    seen.add(k)
+                    objs.append((path, r))
+            errors = {}                      # position at this depth -> ErrCorrupt
+            trees = {}                       # position -> the tree's bytes
+            single = {}                      # type -> positions
+            for i, (path, r) in enumerate(objs):
+                root, salt = r.root, self.make_salt(r.type)
+                try:
+                    if root.size == 0:
+                        bigblob._check_empty(root.ref, salt, cid_key, store.get(root.ref.cid))
+                        checked += 1
+                    elif root.size <= min(root.block_size, self.MAX_OPEN_BLOB):
+                        single.setdefault(r.type, []).append(i)
+                    elif r.type == TYPE_TREE:
+                        trees[i] = bigblob.read_all(store, root, salt=salt, cid_key=cid_key)
+                        checked += _blob_count(root)
+                    else:
+                        checked += self.bbag.verify(store, root, salt=salt, cid_key=cid_key)
+                except bigblob.ErrCorrupt as e:
+                    errors[i] = e
+            for ty, idx in single.items():
+                raw = bigblob.derive_key(self.make_salt(ty), b"raw")
+                want = ty == TYPE_TREE
+                j = 0
+                while j < len(idx):
+                    part, size = [], 0
+                    while j < len(idx) and (not part or size + objs[idx[j]][1].root.size
+                                            <= self.VERIFY_BATCH_BYTES):
+                        part.append(idx[j])
+                        size += objs[idx[j]][1].root.size
+                        j += 1
+                    cts = [store.get(objs[i][1].root.ref.cid) for i in part]
+                    # stored bytes of another length are not the blob's: not sent
+                    ok = [i for i, c in zip(part, cts) if len(c) == objs[i][1].root.size]
+                    for i in set(part) - set(ok):
+                        errors[i] = bigblob.ErrCorrupt(0, objs[i][1].root.ref.cid,
+                                                       bigblob.N.GLFSX_BAD_CID, 0)
+                    okc = [c for i, c in zip(part, cts) if len(c) == objs[i][1].root.size]
+                    pts, sts = bigblob.open_blobs(okc, [objs[i][1].root.ref for i in ok], raw,
+                                                  cid_key, want_ptext=want)
+                    for n, (i, st) in enumerate(zip(ok, sts)):
+                        if st:
+                            errors[i] = bigblob.ErrCorrupt(n, objs[i][1].root.ref.cid, st, 0)
+                        elif want:
+                            trees[i] = pts[n]
+                    checked += len(ok)
+            if errors:
+                i = min(errors)
+                errors[i].path = objs[i][0]
+                raise errors[i]
+            frontier = []
+            for i in sorted(trees):
+                base = objs[i][0]
+                frontier += [((base + "/" + e.name) if base else e.name, e.ref)
+                             for e in read_tree_bytes(trees[i])]
+        return checked
 
     def get_at_path(self, store, ref: Ref, subpath: str) -> Ref:
         """tree.go:91-99 GetAtPath (ErrNoEnt when nothing is at subpath)."""

@@ -27,6 +27,10 @@
  *   glfsx_post_ragged_device
  *                          bigblob/ref.go:98-111   (*Machine).post, batched over
  *                          messages of unequal length, minus the store.Post call
+ *   glfsx_open_ragged_device,
+ *   glfsx_open_blobs       bigblob/ref.go:113-126  getF with its checks, batched
+ *                          over messages of unequal length (what the ragged post
+ *                          and glfsx_post_blobs wrote)
  *   glfsx_depth            bigblob/blob.go:256-264 depth()
  *   glfsx_tree_encode      tree.go:300-316 TreeWriter.Put's JSON lines, batched
  *   glfsx_store_*          the store under ref.go:103 (bcsdk.WO / MemStore [ext])
@@ -544,7 +548,40 @@ int glfsx_open_batch_device(const uint8_t *salt, const uint8_t *cid_key,
 int glfsx_open_batch(const uint8_t *salt, const uint8_t *cid_key, const void *ctext,
                      uint64_t total, uint64_t block_size, const uint8_t *refs,
                      void *ptext, uint32_t *status_out, uint64_t *n_bad);
-/* Test hook: the route of the two calls above -- 0 auto, 1 always the
+/* The verified read batched over n messages of unequal length (what
+ * glfsx_post_ragged_device and glfsx_post_blobs wrote): message i =
+ * d_ctext[d_offsets[i] .. +d_lengths[i]), 0 <= length <= 16 MiB, is checked
+ * against the 64-byte ref at d_refs + 64 i; d_status[i] (every i, no
+ * pre-zeroing needed) = GLFSX_BAD_CID | GLFSX_BAD_DEK as above, and the
+ * plaintext goes to d_ptext (nullable: check only; may equal d_ctext -- the
+ * messages must be disjoint then, otherwise they may overlap or repeat) at
+ * the same offsets.  `salt` is taken as given (the level's salt; no
+ * derivation and no empty-blob rule; NULL = no DEK check).  max_len bounds
+ * the lengths: a longer message is neither read nor written and its status
+ * is GLFSX_BAD_CID.  Checked before the device is touched, in this order: a
+ * null d_ctext, d_refs or d_status, then a d_refs or d_status that is not
+ * 4-byte aligned (GLFSX_E_ARG), max_len above 16 MiB (GLFSX_E_UNSUPPORTED),
+ * n == 0 (returns 0).  Device pointers; enqueued on stream, which is waited
+ * for once (the plan's totals) and not synchronised after that; at most five
+ * launches whatever n. */
+int glfsx_open_ragged_device(const uint8_t *salt, const uint8_t *cid_key,
+                             const void *d_ctext, const uint64_t *d_offsets,
+                             const uint64_t *d_lengths, uint64_t n, uint64_t max_len,
+                             const void *d_refs, void *d_ptext, uint32_t *d_status,
+                             void *stream);
+/* The same over host memory: the messages go through the device in groups of
+ * whole consecutive messages of at most 64 MiB, gathered into pinned staging,
+ * and the plaintext is scattered back to ptext + offsets[i] (no other byte of
+ * ptext is written).  A length above 16 MiB: GLFSX_E_UNSUPPORTED before any
+ * work.  ptext, status_out and n_bad (the number of bad messages) are
+ * nullable.  Returns GLFSX_E_CORRUPT if any message failed: every message
+ * has been processed and the outputs are complete by then, and
+ * glfsx_last_error names the first bad message and the checks it failed. */
+int glfsx_open_blobs(const uint8_t *salt, const uint8_t *cid_key, const void *ctext,
+                     const uint64_t *offsets, const uint64_t *lengths, uint64_t n,
+                     const uint8_t *refs, void *ptext, uint32_t *status_out,
+                     uint64_t *n_bad);
+/* Test hook: the route of glfsx_open_batch[_device] -- 0 auto, 1 always the
  * composed passes, 2 the one-pass kernel wherever it is able.  Any other
  * value changes nothing.  Returns the previous value; process-wide. */
 int glfsx_set_open_route(int route);
