@@ -130,6 +130,7 @@ SIGNATURES = {
                                         _VP]),
     "glfsx_open_blobs": (_INT, [_CP, _CP, _VP, _VP, _VP, _U64, _VP, _VP, _VP,
                                 ctypes.POINTER(ctypes.c_uint64)]),
+    "glfsx_open": (_INT, [_CP, _CP, _VP, _VP, _U64, _VP, _VP]),
     "glfsx_set_open_route": (_INT, [_INT]),
     "glfsx_sink_count": (_INT, [_VP, _INT, _VP, _VP, _U64]),
     "glfsx_tree_encode": (_INT, [_U64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U64,
@@ -214,8 +215,8 @@ def set_latency_wgs(wgs: int) -> int:
 
 def set_open_route(route: int) -> int:
     """Test hook (include/glfsx.h): the verified read's route -- 0 auto, 1 the
-    composed passes, 2 the one-pass kernel wherever able.  Returns the
-    previous value."""
+    composed passes (glfsx_open: every size through device staging), 2 the
+    one-pass kernel wherever able.  Returns the previous value."""
     return lib.glfsx_set_open_route(route)
 
 

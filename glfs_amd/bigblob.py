@@ -342,30 +342,71 @@ class Machine:
         self.block_size = block_size
         self.cache_size = cache_size
         # machine.go:36 getF LRU, keyed by Ref.Key() (= BLAKE3(CID||DEK) in
-        # the reference; the 64-B ref itself identifies the same entry)
-        self._cache: "OrderedDict[bytes, bytes]" = OrderedDict()
+        # the reference; the 64-B ref itself identifies the same entry).  An
+        # entry is (plaintext, checks): None for an unchecked read, else the
+        # (cid_key, level salt) it passed glfsx_open under
+        self._cache: "OrderedDict[bytes, tuple]" = OrderedDict()
+        self._salts: dict = {}   # blob salt -> (indexSalt, rawSalt)
 
     # ------------------------------------------------------------ read side
-    def get_f(self, store, ref: Ref) -> bytes:
+    def _level_salts(self, salt: Optional[bytes]) -> tuple:
+        """blob.go:99-101: (indexSalt, rawSalt) of a blob's salt, derived once
+        per Machine and salt (derive_key is a GPU call); (None, None) for no
+        salt."""
+        if salt is None:
+            return None, None
+        salt = _salt_arg(salt)
+        got = self._salts.get(salt)
+        if got is None:
+            if len(self._salts) >= 64:
+                self._salts.clear()
+            got = self._salts[salt] = (derive_key(salt, b"index"), derive_key(salt, b"raw"))
+        return got
+
+    def get_f(self, store, ref: Ref, salt: Optional[bytes] = None,
+              cid_key: Optional[bytes] = None) -> bytes:
         """ref.go:113-126 getF: fetch the ctext by CID, decrypt with the DEK
-        (ChaCha20 on the GPU), cache the plaintext."""
+        (ChaCha20 on the GPU), cache the plaintext.  With salt (the level's
+        salt as post took it: rawSalt or indexSalt) or cid_key (the store's)
+        the block goes through glfsx_open instead: its bytes must hash to the
+        CID (keyed by cid_key) and, when salt is given, its plaintext to the
+        DEK; a bad block raises ErrCorrupt and never enters the cache, and a
+        cached plaintext serves a checked read only if it passed the same
+        checks."""
         key = ref.marshal_binary()
+        checked = salt is not None or cid_key is not None
+        want = (cid_key, _salt_arg(salt)) if checked else None
         hit = self._cache.get(key)
         if hit is not None:
-            self._cache.move_to_end(key)
-            return hit
-        data = crypto_xor(ref.dek, store.get(ref.cid))
+            have = hit[1]
+            if not checked or (have is not None and have[0] == want[0]
+                               and want[1] in (None, have[1])):
+                self._cache.move_to_end(key)
+                return hit[0]
+        if checked:
+            data = open_block(store.get(ref.cid), ref, salt, cid_key)
+        else:
+            data = crypto_xor(ref.dek, store.get(ref.cid))
         if self.cache_size > 0:
-            self._cache[key] = data
+            self._cache[key] = (data, want)
+            self._cache.move_to_end(key)
             if len(self._cache) > self.cache_size:
                 self._cache.popitem(last=False)
         return data
 
-    def get_piece(self, store, root: Ref, bf: int, level: int, block_index: int) -> Ref:
+    def get_piece(self, store, root: Ref, bf: int, level: int, block_index: int,
+                  salt: Optional[bytes] = None, cid_key: Optional[bytes] = None) -> Ref:
         """blob.go:53-69 getPiece: walk index nodes down to the block's ref.
-        Index nodes must be exactly bf*64 bytes (newIndexUsing)."""
+        Index nodes must be exactly bf*64 bytes (newIndexUsing).  With salt
+        (the blob's, as Create took it) or cid_key every node on the way is
+        checked under DeriveKey(salt, "index") (get_f); a bad node raises
+        ErrCorrupt with its level."""
+        index_salt = self._level_salts(salt)[0]
         while level > 0:
-            data = self.get_f(store, root)
+            try:
+                data = self.get_f(store, root, index_salt, cid_key)
+            except ErrCorrupt as e:
+                raise e.at_level(level) from None
             if len(data) != bf * MAX_REF_SIZE:
                 raise ValueError("data is not correct size for index")
             span = bf ** (level - 1)
@@ -375,45 +416,62 @@ class Machine:
             level -= 1
         return root
 
-    def read_at(self, store, x: Root, offset: int, n: int) -> tuple:
+    def read_at(self, store, x: Root, offset: int, n: int, salt: Optional[bytes] = None,
+                cid_key: Optional[bytes] = None) -> tuple:
         """blob.go:31-51 ReadAt: at most ONE block per call (quirk kept).
         Returns (data, eof) where eof mirrors the io.EOF the reference
-        returns when the read ends exactly at Size."""
+        returns when the read ends exactly at Size.  With salt (the blob's) or
+        cid_key the index nodes and the data block are checked as they are
+        read (get_piece, get_f): the data block under DeriveKey(salt, "raw"),
+        the empty blob under the index salt; ErrCorrupt carries the bad
+        blob's CID and level."""
         level = depth(x.size, x.block_size)
         bf = branching_factor(x.block_size)
         block_index, rel = divmod(offset, x.block_size)
-        ref = self.get_piece(store, x.ref, bf, level, block_index)
-        data = self.get_f(store, ref)
+        ref = self.get_piece(store, x.ref, bf, level, block_index, salt, cid_key)
+        index_salt, raw_salt = self._level_salts(salt)
+        try:
+            data = self.get_f(store, ref, index_salt if x.size == 0 else raw_salt, cid_key)
+        except ErrCorrupt as e:
+            raise e.at_level(0) from None
         if rel > len(data):  # Go slices data[relOffset:] and panics
             raise Panic(N.GLFSX_E_ARG, "slice bounds out of range")
         out = data[rel:rel + n]
         return out, offset + len(out) == x.size
 
-    def new_reader(self, store, root: Root) -> "Reader":
-        """io.go:23-30."""
-        return Reader(self, store, root)
+    def new_reader(self, store, root: Root, salt: Optional[bytes] = None,
+                   cid_key: Optional[bytes] = None) -> "Reader":
+        """io.go:23-30 (salt / cid_key: a Reader whose every read is checked,
+        see read_at)."""
+        return Reader(self, store, root, salt, cid_key)
 
-    def traverse(self, store, root: Root, enter, exit) -> None:
+    def traverse(self, store, root: Root, enter, exit, salt: Optional[bytes] = None,
+                 cid_key: Optional[bytes] = None) -> None:
         """traverse.go:18-52: pre-order Enter(cid) -> bool (False skips the
         subtree), post-order Exit(level, ref).  Children stop at the first
-        all-zero CID."""
+        all-zero CID.  With salt (the blob's) or cid_key every index node is
+        checked as it is read (get_f under DeriveKey(salt, "index"))."""
         if root.block_size == 0:
             raise ValueError("block size cannot be zero")
         self._traverse(store, root.block_size, depth(root.size, root.block_size),
-                       root.ref, enter, exit)
+                       root.ref, enter, exit, self._level_salts(salt)[0], cid_key)
 
-    def _traverse(self, store, bs, level, x: Ref, enter, exit) -> None:
+    def _traverse(self, store, bs, level, x: Ref, enter, exit, index_salt=None,
+                  cid_key=None) -> None:
         if not enter(x.cid):
             return
         if level > 0:
-            data = self.get_f(store, x)
+            try:
+                data = self.get_f(store, x, index_salt, cid_key)
+            except ErrCorrupt as e:
+                raise e.at_level(level) from None
             if len(data) != bs:
                 raise ValueError("data is not correct size for index")
             for i in range(bs // MAX_REF_SIZE):
                 r2 = Ref.from_bytes(data[i * MAX_REF_SIZE:(i + 1) * MAX_REF_SIZE])
                 if r2.cid == bytes(CID_SIZE):
                     break
-                self._traverse(store, bs, level - 1, r2, enter, exit)
+                self._traverse(store, bs, level - 1, r2, enter, exit, index_salt, cid_key)
         exit(level, x)
 
     def sync(self, dst, src, x: Root, fn=None, verify: bool = False,
@@ -499,11 +557,13 @@ class Machine:
                 raise ErrCorrupt(j + e.index, e.cid, e.status, 0) from None
         return sum(len(lv) for lv in levels)
 
-    def populate(self, store, root: Root, dst) -> None:
+    def populate(self, store, root: Root, dst, salt: Optional[bytes] = None,
+                 cid_key: Optional[bytes] = None) -> None:
         """blob.go:317-331 Populate: add every reachable CID that dst lacks
-        (Enter skips subtrees dst already has; Exit adds)."""
+        (Enter skips subtrees dst already has; Exit adds).  salt / cid_key:
+        the index nodes are checked as traverse reads them."""
         self.traverse(store, root, lambda cid: not exists_unit(dst, cid),
-                      lambda level, ref: dst.add(ref.cid))
+                      lambda level, ref: dst.add(ref.cid), salt, cid_key)
 
     def post(self, store: WO, salt: Optional[bytes], data: bytes,
              cid_key: Optional[bytes] = None) -> Ref:
@@ -598,14 +658,19 @@ def _concat(machine: "Machine", store, block_size: int, salt, roots, cid_key=Non
 
 class Reader:
     """io.go:15-54 Reader: Read / ReadAt / Seek over a Root (each call reads
-    from at most one block, as the reference's ReadAt does)."""
+    from at most one block, as the reference's ReadAt does).  With salt (the
+    blob's, as Create took it) or cid_key (the store's) every block and index
+    node a read touches is checked (Machine.read_at) and a bad one raises
+    ErrCorrupt instead of coming back as data."""
     SEEK_SET, SEEK_CUR, SEEK_END = 0, 1, 2
 
-    def __init__(self, machine: Machine, store, root: Root):
+    def __init__(self, machine: Machine, store, root: Root, salt: Optional[bytes] = None,
+                 cid_key: Optional[bytes] = None):
         self.o, self.store, self.root, self.offset = machine, store, root, 0
+        self.salt, self.cid_key = salt, cid_key
 
     def read_at(self, n: int, at: int) -> tuple:
-        return self.o.read_at(self.store, self.root, at, n)
+        return self.o.read_at(self.store, self.root, at, n, self.salt, self.cid_key)
 
     def read(self, n: int = -1) -> bytes:
         """Python io semantics on top of ReadAt: returns b"" at EOF; n < 0
@@ -617,7 +682,7 @@ class Reader:
             while self.offset < self.root.size:
                 parts.append(self.read(self.root.size - self.offset))
             return b"".join(parts)
-        data, _ = self.o.read_at(self.store, self.root, self.offset, n)
+        data, _ = self.o.read_at(self.store, self.root, self.offset, n, self.salt, self.cid_key)
         self.offset += len(data)
         return data
 
@@ -807,6 +872,24 @@ def crypto_xor(dek: bytes, data: bytes) -> bytes:
     out = ctypes.create_string_buffer(max(len(data), 1))
     N.check(N.lib.glfsx_chacha20_xor(bytes(dek), data, out, len(data)))
     return out.raw[:len(data)]
+
+
+def open_block(ctext, ref: Ref, salt: Optional[bytes], cid_key: Optional[bytes] = None,
+               want_ptext: bool = True) -> bytes:
+    """getF with its checks for one block (glfsx_open; ref.go:113-126): ctext
+    must hash to ref's CID (keyed by cid_key) and, when salt is given (the
+    level's salt as post took it), its plaintext to ref's DEK.  One launch up
+    to 64 KiB.  Returns the plaintext (b"" when want_ptext is false); raises
+    ErrCorrupt(0, cid, status)."""
+    ctext = bytes(ctext)
+    out = ctypes.create_string_buffer(max(len(ctext), 1)) if want_ptext else None
+    st = ctypes.c_uint32(0)
+    rc = N.lib.glfsx_open(_salt_arg(salt), cid_key, ref.marshal_binary(), ctext, len(ctext),
+                          out, ctypes.byref(st))
+    if rc == N.GLFSX_E_CORRUPT:
+        raise ErrCorrupt(0, ref.cid, st.value)
+    N.check(rc)
+    return out.raw[:len(ctext)] if want_ptext else b""
 
 
 def decrypt_level(ctexts, refs, block_size: int) -> list:

@@ -326,11 +326,16 @@ inline void set_keys(SmallJob &j, const Salts &s, const uint8_t *cid_key) {
 }
 
 // ---- oneshot.cpp ----
-// A one-shot post's request: fill in d (src, ctext, ref, len, present and
-// the keys); the rest belongs to the poster.
+// A one-shot request: a post -- fill in d (src, ctext, ref, len, present and
+// the keys) -- or, with open set, a verified read -- fill in o (src, ptext,
+// status, ref, len and the keys) and salted; the rest belongs to the poster.
 struct OneLane;
 struct OneReq {
   OneDesc d{};
+  bool open = false;    // the request's kind
+  bool salted = false;  // an open that checks the DEK too
+  OneOpenDesc o{};
+  uint32_t len() const { return open ? o.len : d.len; }
   OneReq *next = nullptr;     // the pending stack
   std::atomic<int> armed{0};  // flag / seq / lane below are set (by the leader)
   std::atomic<int> done{0};   // failed before launch (rc, err)
@@ -341,8 +346,9 @@ struct OneReq {
   std::string err;
 };
 constexpr uint64_t kMedBatchBytes = 64ull << 20;  // device copies per launch
-// Post rs[0..n) on device dev (the calling thread's current device); returns
-// when every request's ctext and ref are in its staging.
+// Run rs[0..n) on device dev (the calling thread's current device); returns
+// when every request's results (ctext and ref; plaintext and status) are in
+// its staging.  Posts and opens of concurrent callers share launches.
 int one_post_many(int dev, OneReq *const *rs, size_t n);
 
 // Post one message of at most kMaxMedLen bytes from host memory (ref.go:98
@@ -357,6 +363,13 @@ int post_host_message(int dev, OneStaging st, const uint8_t salt[32], const uint
                       const uint8_t *data, uint64_t n, bool want_ctext, uint8_t ref[64],
                       glfsx_post_fn post = nullptr, void *post_ctx = nullptr, int kind = 0,
                       const PinBuf *pin = nullptr, uint64_t present = ~0ull);
+// getF with its checks (ref.go:113-126) for one block of at most kMaxOneLen
+// bytes from host memory, as a one-shot open: the ctext is copied into h_in,
+// the plaintext (if ptext) comes back through h_ct and the status word
+// through h_ref.  salt null: the CID check only.  ptext may equal ctext.
+int open_host_message(int dev, OneStaging st, const uint8_t *salt, const uint8_t *cid_key,
+                      const uint8_t ref[64], const uint8_t *ctext, uint64_t n, void *ptext,
+                      uint32_t *status);
 // The same for a message of any length through device staging on stream s:
 // the ref is downloaded to ref_dst and the ctext to ct_dst (nullable), and
 // the stream waited for.  src_ready set: `data` is device memory written on

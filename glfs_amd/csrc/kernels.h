@@ -1,8 +1,9 @@
 // kernels.h -- internal interface between the host runtime (host.h and its
 // units: runtime, oneshot, copy_pool, writer, create, blobs, read) and the
 // gfx950 kernels: post_kernels.hip (the launches, with its fragments b3_arx.h,
-// pass_kernels.h, quad_kernels.h, one_kernels.h, small_kernels.h,
-// ragged_kernels.h, read_kernels.h, open_kernels.h and ragged_open_kernels.h
+// pass_kernels.h, quad_kernels.h, one_kernels.h, one_open_kernels.h,
+// small_kernels.h, ragged_kernels.h, read_kernels.h, open_kernels.h and
+// ragged_open_kernels.h
 // holding the kernels by family; ragged_groups.h the host form's grouping,
 // launch_plan.h the shape of a bulk launch and stream_scratch.h the
 // per-stream scratch its host half keeps, both free of device code),
@@ -171,6 +172,34 @@ hipError_t launch_med(const OneDesc *descs, uint32_t n, uint64_t max_len,
 // or kMaxOneLen < d.len <= kMaxMedLen (launch_med_v).
 hipError_t launch_one_v(const OneDesc &d, hipStream_t s);
 hipError_t launch_med_v(const OneDesc &d, hipStream_t s);
+
+// One-shot verified read (one_open_kernels.h; ref.go:113-126 getF with its
+// checks for one block of at most kMaxOneLen bytes): one workgroup stages the
+// ctext from the caller's pinned staging, decrypts it with the ref's DEK and
+// hashes ctext and plaintext side by side; *status = 1 (CID mismatch) | 2
+// (DEK mismatch), 0 when good, written every time; the plaintext is written
+// either way.  The salted form (launch_one_open's `salted`) checks both, the
+// other one the CID alone (salt is not read, bit 1 never set).  A type of
+// its own: k_one stages OneDesc into LDS by word count.
+struct OneOpenDesc {
+  const uint8_t *src;  // the ctext: 16-B aligned, device-accessible
+  uint8_t *ptext;      // nullable (check only), device-accessible, 16-B aligned
+  uint32_t *status;    // one word out, 4-B aligned
+  uint32_t ref[16];    // the ref's words: CID then DEK
+  uint32_t len;        // <= kMaxOneLen
+  uint32_t cid_keyed;
+  uint32_t salt[8];     // DEK key words (the salted form)
+  uint32_t cid_key[8];  // CID key words (IV when unkeyed)
+  // as OneDesc's: set to seq once status and plaintext are in place
+  uint32_t *flag;
+  uint32_t seq;
+};
+// descs: n descriptors in device-accessible memory, all salted or all not;
+// max_len bounds their len.
+hipError_t launch_one_open(const OneOpenDesc *descs, uint32_t n, uint64_t max_len, bool salted,
+                           hipStream_t s);
+// One request, its descriptor passed by value.
+hipError_t launch_one_open_v(const OneOpenDesc &d, bool salted, hipStream_t s);
 
 // Read side: decrypt n contiguous blocks (bs % 64 == 0; the last one
 // last_len bytes) with the DEKs in bytes [32,64) of refs[j] (dense).

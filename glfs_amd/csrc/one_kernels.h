@@ -138,14 +138,14 @@ __device__ __forceinline__ void one_hash(uint32_t &cl, uint32_t &ch, uint32_t im
 // Every lane's loads are issued before any is waited for: the source is
 // the caller's pinned staging, one PCIe round trip (~1.7 us) per wave of
 // loads, which a loop that waits per iteration paid 4x at 4 KiB and 16x at
-// 16 KiB.  padded <= 16 x LANES x 16 B (k_one<16>: 16 KiB, k_one<64> and a
-// k_med span: 64 KiB).
-template <int LANES>
+// 16 KiB.  padded <= IT x LANES x 16 B (k_one<16>: 16 KiB, k_one<64> and a
+// k_med span: 64 KiB; k_one_open's salted forms have twice the lanes and
+// IT = 8).
+template <int LANES, int IT = 16>
 __device__ __forceinline__ void one_stage(uint4 *img_u4, const uint8_t *src, uint32_t len,
                                           uint32_t present, uint8_t *dcopy) {
   const uint32_t padded = len ? (len + 63) & ~63u : 64u;
   const uint32_t have = min(len, present);
-  constexpr int IT = 16;
   uint4 v[IT];
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
@@ -212,9 +212,11 @@ __device__ __forceinline__ void one_store(const uint4 *img_u4, uint8_t *dst, uin
 // post's critical path: round 5's k_one waited for the salt words after the
 // message, then for the CID key, the output pointers, the flag and the
 // sequence number (s_load ... s_waitcnt pairs in the code object).
-__device__ __forceinline__ const OneDesc *one_desc(OneDesc *s, const OneDesc *g) {
-  constexpr uint32_t kW = sizeof(OneDesc) / 4;
-  static_assert(sizeof(OneDesc) % 4 == 0 && kW <= 64, "wave 0 stages the descriptor");
+// D: OneDesc, or k_one_open's OneOpenDesc.
+template <class D>
+__device__ __forceinline__ const D *one_desc(D *s, const D *g) {
+  constexpr uint32_t kW = sizeof(D) / 4;
+  static_assert(sizeof(D) % 4 == 0 && kW <= 64, "wave 0 stages the descriptor");
   if (threadIdx.x < kW)
     reinterpret_cast<uint32_t *>(s)[threadIdx.x] =
         reinterpret_cast<const uint32_t *>(g)[threadIdx.x];
@@ -226,7 +228,8 @@ __device__ __forceinline__ const OneDesc *one_desc(OneDesc *s, const OneDesc *g)
 // stores are done, then one release store of the descriptor's sequence
 // number into its flag (pinned host memory) tells the waiting caller, with
 // no stream query (OneDesc::flag; nullable).
-__device__ __forceinline__ void one_signal(const OneDesc *dp) {
+template <class D>
+__device__ __forceinline__ void one_signal(const D *dp) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0 && dp->flag)

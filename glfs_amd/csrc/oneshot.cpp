@@ -6,6 +6,7 @@
 #include <thread>
 
 #include "host.h"
+#include "one_classes.h"
 
 namespace glfsx {
 namespace host {
@@ -33,6 +34,8 @@ struct OneLane {
   uint32_t seq = 0;           // the last launch's sequence number
   OneDesc *h_desc = nullptr;  // pinned, kOneBatch descriptors
   OneDesc *d_desc = nullptr;  // the kernel's view of h_desc
+  OneOpenDesc *h_odesc = nullptr;  // pinned, kOneBatch open descriptors
+  OneOpenDesc *d_odesc = nullptr;
   // pinned, kOneBatch flags + one nobody waits on (glfsx_debug_one_drop)
   uint32_t *h_flag = nullptr, *d_flag = nullptr;
   // medium posts: device copies of the messages, and per descriptor
@@ -66,26 +69,32 @@ int poster_get(int dev, OnePoster **out) {
   auto *p = new OnePoster();
   p->dev = dev;
   for (OneLane &l : p->lane) {
-    void *h = nullptr, *d = nullptr, *hf = nullptr, *df = nullptr;
+    void *h = nullptr, *d = nullptr, *hf = nullptr, *df = nullptr, *ho = nullptr, *dox = nullptr;
     if (hipStreamCreateWithFlags(&l.s, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&l.ev, hipEventDisableTiming) != hipSuccess ||
         hipHostMalloc(&h, sizeof(OneDesc) * kOneBatch, hipHostMallocDefault) != hipSuccess ||
         hipHostGetDevicePointer(&d, h, 0) != hipSuccess ||
+        hipHostMalloc(&ho, sizeof(OneOpenDesc) * kOneBatch, hipHostMallocDefault) != hipSuccess ||
+        hipHostGetDevicePointer(&dox, ho, 0) != hipSuccess ||
         hipHostMalloc(&hf, sizeof(uint32_t) * (kOneBatch + 1), hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer(&df, hf, 0) != hipSuccess) {
       for (OneLane &x : p->lane) {
         if (x.h_desc) (void)hipHostFree(x.h_desc);
+        if (x.h_odesc) (void)hipHostFree(x.h_odesc);
         if (x.h_flag) (void)hipHostFree(x.h_flag);
         if (x.s) (void)hipStreamDestroy(x.s);
         if (x.ev) (void)hipEventDestroy(x.ev);
       }
       if (h && h != static_cast<void *>(l.h_desc)) (void)hipHostFree(h);
+      if (ho) (void)hipHostFree(ho);
       if (hf) (void)hipHostFree(hf);
       delete p;
       return fail(GLFSX_E_DEVICE, "one-shot post setup failed on device %d", dev);
     }
     l.h_desc = static_cast<OneDesc *>(h);
     l.d_desc = static_cast<OneDesc *>(d);
+    l.h_odesc = static_cast<OneOpenDesc *>(ho);
+    l.d_odesc = static_cast<OneOpenDesc *>(dox);
     l.h_flag = static_cast<uint32_t *>(hf);
     l.d_flag = static_cast<uint32_t *>(df);
     memset(hf, 0, sizeof(uint32_t) * (kOneBatch + 1));
@@ -109,60 +118,67 @@ void pending_push(OnePoster *P, OneReq *r) {
 // caller may return while a request of its call is still queued.
 std::atomic<uint32_t> g_one_drop{~0u};
 
-// One launch of k_one over the batch's small messages and one launch_med
-// (two kernels) over its medium ones, on the lane's stream; request i's
-// flag is lane.h_flag[i], set to `seq` when its results are in place.
+// The batch's classes (one_classes.h) each in their own descriptor range,
+// and one launch per class present on the lane's stream: k_one over the small
+// posts, launch_med (two kernels) over the medium ones, k_one_open over the
+// opens without and with a DEK check; request k's flag is lane.h_flag[k], set
+// to `seq` when its results are in place.
 int one_launch(OneLane &L, const std::vector<OneReq *> &batch, uint32_t seq) {
   const uint32_t drop = g_one_drop.exchange(~0u, std::memory_order_relaxed);
-  uint64_t max_small = 0, max_med = 0, med_bytes = 0;
-  size_t ns = 0, nm = 0;
-  for (const OneReq *r : batch) {
-    if (r->d.len <= kMaxOneLen) {
-      ++ns;
-      max_small = std::max<uint64_t>(max_small, r->d.len);
-    } else {
-      ++nm;
-      max_med = std::max<uint64_t>(max_med, r->d.len);
-      med_bytes += (r->d.len + 255) & ~uint64_t(255);
-    }
-  }
+  std::vector<OneItem> items(batch.size());
+  for (size_t k = 0; k < batch.size(); ++k)
+    items[k] = OneItem{batch[k]->open, batch[k]->salted, batch[k]->len()};
+  const OneLayout lay = one_layout(items.data(), items.size(), kMaxOneLen);
+  const uint32_t ns = lay.count[kOneSmall], nm = lay.count[kOneMed];
   if (nm) {
-    if (int e = L.med_msg.ensure(med_bytes)) return e;
+    if (int e = L.med_msg.ensure(lay.med_bytes)) return e;
     if (int e = L.med_aux.ensure(nm * kMedAuxWords * 4)) return e;
     if (L.med_aux.cap > L.aux_zeroed) {  // new buffer: counters must start at zero
       HIP_TRY(hipMemsetAsync(L.med_aux.p, 0, L.med_aux.cap, L.s));
       L.aux_zeroed = L.med_aux.cap;
     }
   }
-  size_t is = 0, im = ns;
-  uint64_t mo = 0;
   for (size_t k = 0; k < batch.size(); ++k) {
     const OneReq *r = batch[k];
-    OneDesc d = r->d;
-    d.flag = L.d_flag + (k == drop ? kOneBatch : k);
-    d.seq = seq;
-    if (r->d.len <= kMaxOneLen) {
-      L.h_desc[is++] = d;
+    uint32_t *const flag = L.d_flag + (k == drop ? kOneBatch : k);
+    const uint32_t slot = lay.slot[k];
+    if (r->open) {
+      OneOpenDesc o = r->o;
+      o.flag = flag;
+      o.seq = seq;
+      L.h_odesc[slot] = o;
       continue;
     }
-    uint32_t *aux = reinterpret_cast<uint32_t *>(L.med_aux.p) + (im - ns) * kMedAuxWords;
-    d.dmsg = L.med_msg.u8() + mo;
-    d.cvs = aux;
-    d.dek = aux + 64 * 8;
-    d.cnt = aux + 64 * 8 + 8;
-    mo += (d.len + 255) & ~uint64_t(255);
-    L.h_desc[im++] = d;
+    OneDesc d = r->d;
+    d.flag = flag;
+    d.seq = seq;
+    if (lay.cls[k] == kOneMed) {
+      uint32_t *aux = reinterpret_cast<uint32_t *>(L.med_aux.p) +
+                      size_t(slot - lay.start[kOneMed]) * kMedAuxWords;
+      d.dmsg = L.med_msg.u8() + lay.med_off[k];
+      d.cvs = aux;
+      d.dek = aux + 64 * 8;
+      d.cnt = aux + 64 * 8 + 8;
+    }
+    L.h_desc[slot] = d;
   }
-  // a launch of one one-shot post (of either size class) passes its
-  // descriptor by value instead of through the pinned descriptor array
+  // a launch of one request (of any class) passes its descriptor by value
+  // instead of through the pinned descriptor array
   if (ns == 1)
     HIP_TRY(launch_one_v(L.h_desc[0], L.s));
   else if (ns)
-    HIP_TRY(launch_one(L.d_desc, uint32_t(ns), max_small, L.s));
+    HIP_TRY(launch_one(L.d_desc, ns, lay.max_len[kOneSmall], L.s));
   if (nm == 1)
     HIP_TRY(launch_med_v(L.h_desc[ns], L.s));
   else if (nm)
-    HIP_TRY(launch_med(L.d_desc + ns, uint32_t(nm), max_med, L.s));
+    HIP_TRY(launch_med(L.d_desc + ns, nm, lay.max_len[kOneMed], L.s));
+  for (const OneClass c : {kOneOpen, kOneOpenSalted}) {
+    const uint32_t n = lay.count[c], at = lay.start[c];
+    if (n == 1)
+      HIP_TRY(launch_one_open_v(L.h_odesc[at], c == kOneOpenSalted, L.s));
+    else if (n)
+      HIP_TRY(launch_one_open(L.d_odesc + at, n, lay.max_len[c], c == kOneOpenSalted, L.s));
+  }
   HIP_TRY(hipEventRecord(L.ev, L.s));
   return 0;
 }
@@ -203,9 +219,15 @@ struct SleepSlack {
 }  // namespace
 
 int one_post_many(int dev, OneReq *const *rs, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (rs[i]->d.len > kMaxMedLen || (reinterpret_cast<uintptr_t>(rs[i]->d.src) & 15))
-      return fail(GLFSX_E_ARG, "one-shot post: bad descriptor");
+  for (size_t i = 0; i < n; ++i) {
+    const OneReq *r = rs[i];
+    const bool bad = r->open ? r->o.len > kMaxOneLen || !r->o.status ||
+                                   ((reinterpret_cast<uintptr_t>(r->o.src) |
+                                     reinterpret_cast<uintptr_t>(r->o.ptext)) & 15)
+                             : r->d.len > kMaxMedLen ||
+                                   (reinterpret_cast<uintptr_t>(r->d.src) & 15);
+    if (bad) return fail(GLFSX_E_ARG, "one-shot post: bad descriptor");
+  }
   OnePoster *P;
   if (int e = poster_get(dev, &P)) return e;
   for (size_t i = 0; i < n; ++i) pending_push(P, rs[i]);
@@ -278,7 +300,7 @@ int one_post_many(int dev, OneReq *const *rs, size_t n) {
         uint64_t mb = 0;
         while (r) {
           OneReq *nx = r->next;
-          const uint64_t len = r->d.len;
+          const uint64_t len = r->len();
           const bool fits = batch.size() < kOneBatch &&
                             (len <= kMaxOneLen || batch.empty() || mb + len <= kMedBatchBytes);
           if (fits) {
@@ -379,6 +401,32 @@ int post_host_message(int dev, OneStaging st, const uint8_t salt[32], const uint
   if (int e = one_post_many(dev, &rp, 1)) return e;
   memcpy(ref, st.h_ref.p, 64);
   return deliver(post, post_ctx, kind, ref, st.h_ct.p, n);
+}
+
+int open_host_message(int dev, OneStaging st, const uint8_t *salt, const uint8_t *cid_key,
+                      const uint8_t ref[64], const uint8_t *ctext, uint64_t n, void *ptext,
+                      uint32_t *status) {
+  if (int e = st.h_in.ensure(n + 64)) return e;
+  if (ptext)
+    if (int e = st.h_ct.ensure(n + 64)) return e;
+  if (int e = st.h_ref.ensure(64)) return e;
+  if (n) par_memcpy(st.h_in.u8(), ctext, n);
+  OneReq r;
+  r.open = true;
+  r.salted = salt != nullptr;
+  r.o.src = st.h_in.dptr();
+  r.o.ptext = ptext ? st.h_ct.dptr() : nullptr;
+  r.o.status = reinterpret_cast<uint32_t *>(st.h_ref.dptr());
+  words_from_key(r.o.ref, ref);
+  words_from_key(r.o.ref + 8, ref + 32);
+  r.o.len = uint32_t(n);
+  if (salt) words_from_key(r.o.salt, salt);
+  set_cid_key(r.o, cid_key);
+  OneReq *rp = &r;
+  if (int e = one_post_many(dev, &rp, 1)) return e;
+  *status = *reinterpret_cast<const uint32_t *>(st.h_ref.p);
+  if (ptext && n) memcpy(ptext, st.h_ct.p, n);
+  return 0;
 }
 
 int post_staged_message(hipStream_t s, DevStaging st, const uint8_t salt[32],

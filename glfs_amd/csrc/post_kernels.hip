@@ -48,6 +48,7 @@ namespace {
 #include "pass_kernels.h"
 #include "quad_kernels.h"
 #include "one_kernels.h"
+#include "one_open_kernels.h"
 #include "small_kernels.h"
 #include "ragged_kernels.h"
 #include "read_kernels.h"
@@ -774,6 +775,50 @@ hipError_t launch_one_v(const OneDesc &d, hipStream_t s) {
     hipLaunchKernelGGL(k_one_v<16>, dim3(1), dim3(64), 0, s, d);
   else
     hipLaunchKernelGGL(k_one_v<64>, dim3(1), dim3(256), 0, s, d);
+  return hipGetLastError();
+}
+
+// k_one_open's workgroup: four lanes per quad, two trees when salted.
+template <int QUADS, bool SALTED>
+constexpr uint32_t one_open_lanes() {
+  return QUADS * (SALTED ? 8 : 4);
+}
+
+hipError_t launch_one_open(const OneOpenDesc *descs, uint32_t n, uint64_t max_len, bool salted,
+                           hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (max_len > kMaxOneLen) return hipErrorInvalidValue;
+  const bool small = max_len <= 16 * 1024;
+  if (salted && small)
+    hipLaunchKernelGGL((k_one_open<16, true>), dim3(n), dim3(one_open_lanes<16, true>()), 0, s,
+                       descs);
+  else if (salted)
+    hipLaunchKernelGGL((k_one_open<64, true>), dim3(n), dim3(one_open_lanes<64, true>()), 0, s,
+                       descs);
+  else if (small)
+    hipLaunchKernelGGL((k_one_open<16, false>), dim3(n), dim3(one_open_lanes<16, false>()), 0, s,
+                       descs);
+  else
+    hipLaunchKernelGGL((k_one_open<64, false>), dim3(n), dim3(one_open_lanes<64, false>()), 0, s,
+                       descs);
+  return hipGetLastError();
+}
+
+hipError_t launch_one_open_v(const OneOpenDesc &d, bool salted, hipStream_t s) {
+  if (d.len > kMaxOneLen) return hipErrorInvalidValue;
+  const bool small = d.len <= 16 * 1024;
+  if (salted && small)
+    hipLaunchKernelGGL((k_one_open_v<16, true>), dim3(1), dim3(one_open_lanes<16, true>()), 0, s,
+                       d);
+  else if (salted)
+    hipLaunchKernelGGL((k_one_open_v<64, true>), dim3(1), dim3(one_open_lanes<64, true>()), 0, s,
+                       d);
+  else if (small)
+    hipLaunchKernelGGL((k_one_open_v<16, false>), dim3(1), dim3(one_open_lanes<16, false>()), 0,
+                       s, d);
+  else
+    hipLaunchKernelGGL((k_one_open_v<64, false>), dim3(1), dim3(one_open_lanes<64, false>()), 0,
+                       s, d);
   return hipGetLastError();
 }
 

@@ -1,5 +1,7 @@
 // read.cpp -- the read side: batched decrypt and verified read ("open") from
 // device or host memory.
+#include <cstdio>
+
 #include "host.h"
 #include "ragged_groups.h"
 
@@ -212,6 +214,54 @@ int glfsx_open_batch(const uint8_t *salt, const uint8_t *cid_key, const void *ct
 }
 
 int glfsx_set_open_route(int route) { return set_open_route(route); }
+
+int glfsx_open(const uint8_t *salt, const uint8_t *cid_key, const uint8_t ref[64],
+               const void *ctext, uint64_t n, void *ptext, uint32_t *status_out) {
+  if (!ref || (n && !ctext)) return fail(GLFSX_E_ARG, "null argument");
+  if (n > kMaxMsgLen)
+    return fail(GLFSX_E_UNSUPPORTED, "message of %llu bytes above the kernels' limit %llu",
+                (unsigned long long)n, (unsigned long long)kMaxMsgLen);
+  Ctx *c;
+  if (int e = ctx_get(&c)) return e;
+  uint32_t status = 0;
+  // route 1 (tests, measurements): every size through device staging
+  const int route = set_open_route(-1);
+  if (n <= kMaxOneLen && route != 1) {
+    if (int e = open_host_message(c->dev, {c->h_oin, c->h_oct, c->h_oref}, salt, cid_key, ref,
+                                  static_cast<const uint8_t *>(ctext), n, ptext, &status))
+      return e;
+  } else {
+    // one upload, launch_open over one block, plaintext and status behind it,
+    // one wait; the ref and the status word share d_refs
+    const uint64_t bs = std::max<uint64_t>(64, (n + 63) & ~63ull);
+    if (int e = c->d_in.ensure(bs + 64)) return e;
+    if (ptext)
+      if (int e = c->d_ct.ensure(bs + 64)) return e;
+    if (int e = c->d_refs.ensure(128)) return e;
+    if (n) HIP_TRY(hipMemcpyAsync(c->d_in.p, ctext, n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_refs.p, ref, 64, hipMemcpyHostToDevice, c->stream));
+    OpenJob job{};
+    open_keys(job, salt, cid_key);
+    job.ctext = c->d_in.u8();
+    job.ptext = ptext ? c->d_ct.u8() : nullptr;
+    job.n = 1;
+    job.bs = bs;
+    job.last_len = n;
+    job.refs = c->d_refs.u8();
+    job.status = reinterpret_cast<uint32_t *>(c->d_refs.u8() + 64);
+    HIP_TRY(launch_open(job, c->stream));
+    if (ptext && n)
+      HIP_TRY(hipMemcpyAsync(ptext, c->d_ct.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&status, job.status, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(stream_wait(c->stream));
+  }
+  if (status_out) *status_out = status;
+  if (!status) return 0;
+  char hex[65];
+  for (int i = 0; i < 32; ++i) snprintf(hex + 2 * i, 3, "%02x", ref[i]);
+  return fail(GLFSX_E_CORRUPT, "blob %s failed its %s check%s", hex,
+              status == 3 ? "CID and DEK" : status == 1 ? "CID" : "DEK", status == 3 ? "s" : "");
+}
 
 int glfsx_open_ragged_device(const uint8_t *salt, const uint8_t *cid_key,
                              const void *d_ctext, const uint64_t *d_offsets,

@@ -49,6 +49,19 @@ def with_salt(salt: bytes):
     return opt
 
 
+def with_verify(cid_key: Optional[bytes] = None):
+    """An option of this mirror (the reference has none): the Machine's reads
+    are verified reads -- get_typed / get_blob / get_blob_bytes return checked
+    Readers under make_salt(type), get_tree_slice / get_at_path read their
+    tree blobs with the verified read_all -- and corrupt bytes raise
+    bigblob.ErrCorrupt.  cid_key: the store's CID key (None: unkeyed).  Off by
+    default: a default-constructed Machine cannot know a store's CID key."""
+    def opt(m: "Machine") -> None:
+        m.verify_reads, m.cid_key = True, cid_key
+    opt.applies = True   # unlike the reference's own options (machine.go:41-48)
+    return opt
+
+
 class TypedWriter:
     """glfs.go:68-92."""
 
@@ -84,6 +97,16 @@ class Machine:
         self.salt = bytes(32)  # opts are ignored (machine.go:41-48)
         self.block_size = DEFAULT_BLOCK_SIZE
         self.bbag = bigblob.Machine(block_size=self.block_size)
+        self.verify_reads, self.cid_key = False, None
+        for opt in opts:       # ... except this mirror's own (with_verify)
+            if getattr(opt, "applies", False):
+                opt(self)
+
+    def _read_kw(self, ty: str) -> dict:
+        """salt= / cid_key= of a verified read of an object of type ty."""
+        if not self.verify_reads:
+            return {}
+        return {"salt": self.make_salt(ty), "cid_key": self.cid_key}
 
     def make_salt(self, ty: str) -> bytes:
         """machine.go:50-54."""
@@ -143,10 +166,11 @@ class Machine:
 
     # ------------------------------------------------------------ read side
     def get_typed(self, store, ty: str, x: Ref) -> bigblob.Reader:
-        """glfs.go:59-66 GetTyped (ty "" accepts any type)."""
+        """glfs.go:59-66 GetTyped (ty "" accepts any type).  A checked Reader
+        under make_salt(x.type) on a Machine made with_verify()."""
         if ty and x.type != ty:
             raise ErrRefType(x.type, ty)
-        return self.bbag.new_reader(store, x.root)
+        return self.bbag.new_reader(store, x.root, **self._read_kw(x.type))
 
     def get_blob(self, store, x: Ref) -> bigblob.Reader:
         """blob.go:20-22, 33-35."""
@@ -268,7 +292,7 @@ class Machine:
     def get_at_path(self, store, ref: Ref, subpath: str) -> Ref:
         """tree.go:91-99 GetAtPath (ErrNoEnt when nothing is at subpath)."""
         from .tree import get_at_path
-        return get_at_path(store, ref, subpath)
+        return get_at_path(store, ref, subpath, **self._read_kw(TYPE_TREE))
 
     # ---------------------------------------------------------------- trees
     def new_tree_writer(self, store, **kw):
@@ -293,7 +317,7 @@ class Machine:
     def get_tree_slice(self, store, ref: Ref, max_ents: int = 10 ** 6, **kw) -> list:
         """tree.go:137-143."""
         from .tree import get_tree_slice
-        return get_tree_slice(store, ref, max_ents, **kw)
+        return get_tree_slice(store, ref, max_ents, **{**self._read_kw(TYPE_TREE), **kw})
 
 
 _default: Optional[Machine] = None

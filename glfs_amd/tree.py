@@ -368,33 +368,40 @@ def read_tree_bytes(data: bytes, cid_from_json=_cid_from_json) -> list:
 
 
 def get_tree_slice(store, ref: glfs.Ref, max_ents: int = 10 ** 6,
-                   cid_from_json=_cid_from_json) -> list:
-    """tree.go:137-143 GetTreeSlice (the read side decrypts on the GPU)."""
+                   cid_from_json=_cid_from_json, salt: Optional[bytes] = None,
+                   cid_key: Optional[bytes] = None) -> list:
+    """tree.go:137-143 GetTreeSlice (the read side decrypts on the GPU).
+    salt (the tree type's, glfs.Machine.make_salt) / cid_key: the tree blob is
+    read with the verified read_all."""
     if ref.type != glfs.TYPE_TREE:
         raise TreeError(f"wrong ref type: have {ref.type} want {glfs.TYPE_TREE}")
-    ents = read_tree_bytes(bigblob.read_all(store, ref.root), cid_from_json)
+    ents = read_tree_bytes(bigblob.read_all(store, ref.root, salt=salt, cid_key=cid_key),
+                           cid_from_json)
     return ents[:max_ents]
 
 
 def lookup_path(store, ent: TreeEntry, subpath: str,
-                cid_from_json=_cid_from_json) -> TreeEntry:
+                cid_from_json=_cid_from_json, salt: Optional[bytes] = None,
+                cid_key: Optional[bytes] = None) -> TreeEntry:
     """tree.go:101-133 Lookup: walk subpath one name at a time through the
     (GPU-decrypted) tree blobs; entries are sorted, so a scan stops at the
-    first name past the wanted one."""
+    first name past the wanted one.  salt / cid_key: as get_tree_slice, for
+    every tree blob on the way."""
     subpath = subpath.strip("/")
     if subpath == "":
         return ent
     if ent.ref.type != glfs.TYPE_TREE:
         raise TreeError("can only take subpath of type tree")
     head, _, rest = subpath.partition("/")
-    for e in get_tree_slice(store, ent.ref, 1 << 62, cid_from_json):
+    for e in get_tree_slice(store, ent.ref, 1 << 62, cid_from_json, salt, cid_key):
         if e.name == head:
-            return lookup_path(store, e, rest, cid_from_json)
+            return lookup_path(store, e, rest, cid_from_json, salt, cid_key)
         if _name_key(e.name) > _name_key(head):
             break
     raise ErrNoEnt(head)
 
 
-def get_at_path(store, ref: glfs.Ref, subpath: str, cid_from_json=_cid_from_json) -> glfs.Ref:
-    """tree.go:91-99 GetAtPath."""
-    return lookup_path(store, TreeEntry("", 0, ref), subpath, cid_from_json).ref
+def get_at_path(store, ref: glfs.Ref, subpath: str, cid_from_json=_cid_from_json,
+                salt: Optional[bytes] = None, cid_key: Optional[bytes] = None) -> glfs.Ref:
+    """tree.go:91-99 GetAtPath (salt / cid_key: as lookup_path)."""
+    return lookup_path(store, TreeEntry("", 0, ref), subpath, cid_from_json, salt, cid_key).ref

@@ -31,6 +31,8 @@
  *   glfsx_open_blobs       bigblob/ref.go:113-126  getF with its checks, batched
  *                          over messages of unequal length (what the ragged post
  *                          and glfsx_post_blobs wrote)
+ *   glfsx_open             bigblob/ref.go:113-126  getF with its checks for one
+ *                          block from host memory: one launch up to 64 KiB
  *   glfsx_depth            bigblob/blob.go:256-264 depth()
  *   glfsx_tree_encode      tree.go:300-316 TreeWriter.Put's JSON lines, batched
  *   glfsx_store_*          the store under ref.go:103 (bcsdk.WO / MemStore [ext])
@@ -581,9 +583,34 @@ int glfsx_open_blobs(const uint8_t *salt, const uint8_t *cid_key, const void *ct
                      const uint64_t *offsets, const uint64_t *lengths, uint64_t n,
                      const uint8_t *refs, void *ptext, uint32_t *status_out,
                      uint64_t *n_bad);
+/* getF with its checks for ONE block from host memory (ref.go:113-126: what
+ * getPiece, ReadAt and a Reader call per block): the n bytes at ctext are
+ * checked against the 64-byte ref (CID || DEK; any alignment) and decrypted
+ * with its DEK into ptext (nullable: check only; may equal ctext) whether or
+ * not the block is good.  *status_out (nullable) = GLFSX_BAD_CID |
+ * GLFSX_BAD_DEK as above, 0 when good.  `salt` is the level's salt as post
+ * took it (no derivation and no empty-blob rule); NULL = no DEK check.
+ * cid_key NULL = an unkeyed CID.  n == 0 is a real message: the CID of the
+ * empty string, and the DEK of the empty string under `salt`.
+ * Up to 64 KiB the block takes one launch of one workgroup (k_one_open),
+ * straight from and to the calling thread's pinned staging, the CID tree over
+ * the ciphertext and the DEK tree over the plaintext side by side; concurrent
+ * callers, and concurrent glfsx_post callers, share launches.  A larger block
+ * goes through the thread's device staging: one upload, the checks of
+ * glfsx_open_batch_device over one block, plaintext and status downloaded
+ * behind it, one wait.
+ * Returns 0, or GLFSX_E_CORRUPT with the outputs complete; glfsx_last_error
+ * then names the CID and the failed checks.  Checked before the device is
+ * touched, in this order: a NULL ref, or n != 0 with a NULL ctext
+ * (GLFSX_E_ARG); n above the kernels' limit of 4 GiB (GLFSX_E_UNSUPPORTED).
+ * Without a device: GLFSX_E_DEVICE. */
+int glfsx_open(const uint8_t *salt, const uint8_t *cid_key, const uint8_t ref[64],
+               const void *ctext, uint64_t n, void *ptext, uint32_t *status_out);
 /* Test hook: the route of glfsx_open_batch[_device] -- 0 auto, 1 always the
- * composed passes, 2 the one-pass kernel wherever it is able.  Any other
- * value changes nothing.  Returns the previous value; process-wide. */
+ * composed passes, 2 the one-pass kernel wherever it is able -- and of
+ * glfsx_open: 1 sends every size through device staging, 0 and 2 take the
+ * one-launch kernel up to 64 KiB.  Any other value changes nothing.  Returns
+ * the previous value; process-wide. */
 int glfsx_set_open_route(int route);
 
 /* --- tree shape (blob.go:219-268) -------------------------------------- */
