@@ -64,6 +64,11 @@ uint64_t fused_timeouts();
 // workgroup since the last reset; reset: zero them after reading.
 // Synchronous (waits for the device).
 hipError_t clock_probe(int reset, uint64_t out[2]);
+// The launch log (launch_log.h), on from the first call: the first min(cap,
+// kept) records of the bulk launches (k_pass, k_quad, k_pass_dc, k_open)
+// since the last reset to out, kLaunchRecWords words each; returns how many
+// were launched since then.  reset: empty the log after reading.  No HIP call.
+size_t pass_log(int reset, uint32_t *out, size_t cap);
 
 // The second half of launch_post alone: ChaCha20 keyed by the DEK already in
 // bytes [32,64) of each ref slot, ctext store, CID into bytes [0,32).

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "launch_log.h"
 #include "launch_plan.h"
 #include "stream_scratch.h"
 
@@ -64,6 +65,18 @@ namespace {
 std::atomic<uint32_t> g_latency_wgs{512};
 uint32_t latency_wgs() { return g_latency_wgs.load(std::memory_order_relaxed); }
 
+// The launch log (glfsx_debug_pass_log): off until first asked for; then
+// every bulk launch site below appends what it launched.  Never destroyed:
+// a launch on another thread may outlive the process's static destructors.
+LaunchLog &g_launch_log = *new LaunchLog();
+inline void log_launch(uint32_t family, int g, bool chacha, bool aligned, int form,
+                       uint32_t split_log2, uint32_t grid, uint64_t n, uint32_t fine_div = 0,
+                       uint64_t items = 0) {
+  if (!g_launch_log.on()) return;
+  g_launch_log.append(LaunchRec{family, uint32_t(g), chacha, aligned, uint32_t(form), split_log2,
+                                grid, fine_div, uint32_t(items), uint32_t(n)});
+}
+
 // From a runtime g to the template parameter G: f(integral_constant<int, G>)
 // for the one of Gs that g equals, hipErrorInvalidValue when it is none.  A
 // left fold: the kernels are instantiated, and so laid out in the code
@@ -89,16 +102,20 @@ hipError_t launch_g(const KArgs &a, bool aligned, hipStream_t s) {
   const bool lat = grid.x <= latency_wgs();
   if (aligned && lat) {
     hipLaunchKernelGGL((k_pass<G, CHACHA, true, 0>), grid, block, 0, s, a);
+    log_launch(kLaunchPass, G, CHACHA, true, 0, a.split_log2, grid.x, a.n);
   } else if (aligned) {
     if constexpr (CHACHA) {
       if (G >= 4 && a.split_log2 == 0) {
         hipLaunchKernelGGL((k_pass<G, true, true, 1>), grid, block, 0, s, a);
+        log_launch(kLaunchPass, G, true, true, 1, a.split_log2, grid.x, a.n);
         return hipGetLastError();
       }
     }
     hipLaunchKernelGGL((k_pass<G, CHACHA, true, 2>), grid, block, 0, s, a);
+    log_launch(kLaunchPass, G, CHACHA, true, 2, a.split_log2, grid.x, a.n);
   } else {
     hipLaunchKernelGGL((k_pass<G, CHACHA, false, 2>), grid, block, 0, s, a);
+    log_launch(kLaunchPass, G, CHACHA, false, 2, a.split_log2, grid.x, a.n);
   }
   return hipGetLastError();
 }
@@ -254,6 +271,7 @@ hipError_t launch_quad(KArgs a, uint64_t maxlen, hipStream_t s) {
     hipLaunchKernelGGL(k_quad<64>, dim3(uint32_t(a.n << sl)), dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL(k_quad<256>, dim3(uint32_t(a.n << sl)), dim3(1024), 0, s, a);
+  log_launch(kLaunchQuad, qpw, false, true, 0, sl, uint32_t(a.n << sl), a.n);
   return hipGetLastError();
 }
 
@@ -496,6 +514,7 @@ hipError_t launch_post_fused(const PostJob &job, hipStream_t s, bool *done) {
   const dim3 grid{uint32_t(items)}, block{256};
   e = with_g<1, 2, 4>(g, [&](auto G) {
     hipLaunchKernelGGL(k_pass_dc<G()>, grid, block, 0, s, a, b, c, d);
+    log_launch(kLaunchPassDc, G(), true, true, 2, sl, grid.x, job.n, d.fine_div, items);
     return hipGetLastError();
   });
   *done = true;
@@ -715,6 +734,11 @@ extern "C" int glfsx_debug_one_timing(int reset, uint64_t out[16]) {
 }
 #endif
 
+size_t pass_log(int reset, uint32_t *out, size_t cap) {
+  if (!g_launch_log.on()) g_launch_log.enable();
+  return g_launch_log.read(reset != 0, out, cap);
+}
+
 hipError_t clock_probe(int reset, uint64_t out[2]) {
   g_clk_on.store(true, std::memory_order_relaxed);
   unsigned long long v[2] = {0, 0};
@@ -925,6 +949,7 @@ static hipError_t launch_open_g(const OArgs &a, bool aligned, hipStream_t s) {
     hipLaunchKernelGGL((k_open<G, true, 2>), grid, block, 0, s, a);
   else
     hipLaunchKernelGGL((k_open<G, false, 2>), grid, block, 0, s, a);
+  log_launch(kLaunchOpen, G, true, aligned, 2, 0, grid.x, a.n);
   return hipGetLastError();
 }
 

@@ -161,6 +161,31 @@ int glfsx_clock_probe(int reset, uint64_t out[2]);
  * them after reading.  out may be NULL. */
 int glfsx_one_stats(int reset, uint64_t out[3]);
 
+/* Test hook (no reference counterpart): which kernel a call really ran.  Off
+ * until first called (a launch then pays one relaxed load); from then on
+ * every bulk hashing launch of the process -- the passes k_pass, k_quad,
+ * k_pass_dc and the verified read's k_open -- appends one record of
+ * GLFSX_PASS_LOG_WORDS uint32_t:
+ *   [0] family: GLFSX_LOG_PASS / _QUAD / _PASS_DC / _OPEN
+ *   [1] G, chunks per lane (k_quad: quads per workgroup, 64 or 256)
+ *   [2] CHACHA: 0 a BLAKE3-only pass, 1 ChaCha20 + CID (k_pass_dc, k_open: 1)
+ *   [3] ALIGNED: 0 the byte-load variant
+ *   [4] ARX form A: 0 compiler-scheduled, 1 quarter-round order, 2 interleaved
+ *   [5] split_log2: log2 workgroups per message
+ *   [6] grid size in workgroups
+ *   [7] k_pass_dc: fine_div (the last ceil(m / fine_div) messages of each
+ *       work list run fine CID items; 0 none); otherwise 0
+ *   [8] k_pass_dc: work items over all lists; otherwise 0
+ *   [9] messages of the launch
+ * as the launch site handed them to the runtime, in launch order.  Copies
+ * the first min(cap, kept) records since the last reset to out (nullable
+ * with cap 0) and writes to *n (nullable) how many were launched since
+ * then: the log keeps the first 4096 and only counts the rest.  reset != 0
+ * empties it after reading.  Process-wide; needs no device. */
+#define GLFSX_PASS_LOG_WORDS 10
+enum { GLFSX_LOG_PASS = 1, GLFSX_LOG_QUAD = 2, GLFSX_LOG_PASS_DC = 3, GLFSX_LOG_OPEN = 4 };
+int glfsx_debug_pass_log(int reset, uint32_t *out, size_t cap, size_t *n);
+
 /* --- primitives -------------------------------------------------------- */
 /* ref.go:152 DeriveKey: BLAKE3 keyed with salt over input (any length),
  * the first out_len bytes of the XOF (any length; blake3.New(len(out), salt)

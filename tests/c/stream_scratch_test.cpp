@@ -1,6 +1,7 @@
-// The launch layer's per-stream scratch (glfs_amd/csrc/stream_scratch.h) and
-// launch plans (launch_plan.h), stand-alone.  Built by tests/test_host_units.py
-// with the host compiler under -fsanitize=address,undefined.  No HIP library
+// The launch layer's per-stream scratch (glfs_amd/csrc/stream_scratch.h),
+// launch plans (launch_plan.h) and launch log (launch_log.h), stand-alone.
+// Built by tests/test_host_units.py with the host compiler under
+// -fsanitize=address,undefined.  No HIP library
 // is linked: the few runtime entry points the header calls are fakes over
 // malloc, defined here, that log their calls and fail on request.
 #include <cstdio>
@@ -9,7 +10,10 @@
 #include <map>
 #include <set>
 #include <string>
+#include <thread>
+#include <vector>
 
+#include "launch_log.h"
 #include "launch_plan.h"
 #include "stream_scratch.h"
 
@@ -316,7 +320,77 @@ static void test_pass_plan() {
   CHECK(quad_qpw(4 << 20) == 64 && quad_qpw((4 << 20) + 1) == 256);
 }
 
+static LaunchRec rec(uint32_t tag) {
+  return LaunchRec{kLaunchPass, tag, tag & 1, 1, 2, 0, tag + 1, 0, 0, tag + 2};
+}
+
+static void test_launch_log() {
+  {
+    LaunchLog log(4);
+    CHECK(!log.on());  // off until enabled: the launch sites append nothing
+    log.enable();
+    CHECK(log.on() && log.kept() == 0);
+    uint32_t out[8 * kLaunchRecWords];
+    memset(out, 0xee, sizeof out);
+    CHECK(log.read(false, out, 8) == 0 && out[0] == 0xeeeeeeeeu);
+    // append: the records come back in order, every word in its place
+    const LaunchRec dc{kLaunchPassDc, 4, 1, 1, 2, 1, 4608, 4, 4608, 1024};
+    log.append(rec(7));
+    log.append(dc);
+    CHECK(log.read(false, out, 8) == 2);
+    const uint32_t want0[kLaunchRecWords] = {kLaunchPass, 7, 1, 1, 2, 0, 8, 0, 0, 9};
+    const uint32_t want1[kLaunchRecWords] = {kLaunchPassDc, 4, 1, 1, 2, 1, 4608, 4, 4608, 1024};
+    CHECK(memcmp(out, want0, sizeof want0) == 0);
+    CHECK(memcmp(out + kLaunchRecWords, want1, sizeof want1) == 0);
+    CHECK(out[2 * kLaunchRecWords] == 0xeeeeeeeeu);  // nothing past the records
+    // a reader's buffer smaller than the log: only that many, the count whole
+    memset(out, 0xee, sizeof out);
+    CHECK(log.read(false, out, 1) == 2 && out[kLaunchRecWords] == 0xeeeeeeeeu);
+    CHECK(log.read(false, nullptr, 0) == 2);
+    // the cap: the first four are kept, the rest only counted
+    for (uint32_t i = 0; i < 5; ++i) log.append(rec(100 + i));
+    CHECK(log.kept() == 4);
+    memset(out, 0xee, sizeof out);
+    CHECK(log.read(true, out, 8) == 7);
+    CHECK(out[3 * kLaunchRecWords + 1] == 101 && out[4 * kLaunchRecWords] == 0xeeeeeeeeu);
+    // reset: empty, still on, and it fills again
+    CHECK(log.on() && log.kept() == 0 && log.read(false, out, 8) == 0);
+    log.append(rec(1));
+    CHECK(log.read(true, out, 8) == 1 && out[1] == 1);
+    CHECK(log.read(false, out, 8) == 0);
+  }
+  {
+    // two threads append at once: every record whole, each thread's in order
+    LaunchLog log(4096);
+    log.enable();
+    auto work = [&log](uint32_t base) {
+      for (uint32_t i = 0; i < 1500; ++i) log.append(rec(base + i));
+    };
+    std::thread a(work, 0u), b(work, 1u << 20);
+    a.join();
+    b.join();
+    std::vector<uint32_t> out(4096 * kLaunchRecWords);
+    CHECK(log.read(false, out.data(), 4096) == 3000 && log.kept() == 3000);
+    uint32_t next[2] = {0, 0};
+    for (size_t i = 0; i < 3000; ++i) {
+      const uint32_t *w = &out[i * kLaunchRecWords];
+      const uint32_t tag = w[1], who = tag >> 20, k = tag & ((1u << 20) - 1);
+      CHECK(who < 2 && k == next[who]);
+      CHECK(w[0] == kLaunchPass && w[2] == (tag & 1) && w[6] == tag + 1 && w[9] == tag + 2);
+      if (who < 2) ++next[who];
+    }
+    CHECK(next[0] == 1500 && next[1] == 1500);
+    // past the cap from two threads: the count is exact, the log is full
+    std::thread c(work, 0u), d(work, 1u << 20);
+    c.join();
+    d.join();
+    CHECK(log.read(true, out.data(), 4096) == 6000);
+    CHECK(log.kept() == 0);
+  }
+}
+
 int main() {
+  test_launch_log();
   test_ensure();
   test_failures();
   test_registry();

@@ -21,9 +21,14 @@ SHAPES = [
     (1088, 3 * 1088),                 # two chunks, the second 64 bytes long
     (128, 7 * 128),                   # whole: ROOT inside lane 0
     (8192, 5 * 8192),                 # exact multiple, no short block
+    (MiB // 2, MiB + 8191),           # G=2
 ]
 BIG = (8 * MiB, 4 * MiB + 64)         # above the fused limit: composed on both routes
 VARIANT_SHAPES = [SHAPES[0], SHAPES[3]]
+UNALIGNED_SHAPES = VARIANT_SHAPES + [SHAPES[7]]   # the byte-load k_open at G = 4, 1 and 2
+# k_open's chunks per lane at each block size of SHAPES (launch_open)
+OPEN_G = {MiB: 4, 2 * MiB: 8, MiB // 2: 2, 65536: 1, 4096: 1, 1088: 1, 128: 1, 8192: 1}
+LOG_OPEN, LOG_WORDS = 4, 10           # GLFSX_LOG_OPEN, GLFSX_PASS_LOG_WORDS
 POISON = 0x5A5A5A5A                   # the status array is not pre-zeroed
 
 
@@ -83,6 +88,22 @@ def _open(N, torch, bs, total, ct, refs, **kw):
     return _collect(torch, _enqueue(N, torch, bs, total, ct, refs, **kw), total, off)
 
 
+def _open_log_reset(N):
+    """Empties the launch log (glfsx_debug_pass_log), which is process-wide
+    and holds whatever earlier tests launched."""
+    N.check(N.lib.glfsx_debug_pass_log(1, None, 0, None))
+
+
+def _open_log(N):
+    """The k_open records of the launch log since _open_log_reset; empties it."""
+    buf = (ctypes.c_uint32 * (LOG_WORDS * 64))()
+    n = ctypes.c_size_t()
+    N.check(N.lib.glfsx_debug_pass_log(1, buf, 64, ctypes.byref(n)))
+    assert n.value <= 64
+    recs = [tuple(buf[i * LOG_WORDS:(i + 1) * LOG_WORDS]) for i in range(n.value)]
+    return [r for r in recs if r[0] == LOG_OPEN]
+
+
 def _flip(b, at, bit=0):
     x = bytearray(b)
     x[at] ^= 1 << bit
@@ -107,7 +128,15 @@ def routes(gpu):
 def test_clean(gpu, O, route, bs, total):
     torch = _torch()
     data, ct, refs = _case(bs, total)
+    _open_log_reset(gpu)
     st, pt, tail = _open(gpu, torch, bs, total, ct, refs)
+    log = _open_log(gpu)
+    if route == 2 and (bs, total) != BIG:
+        # k_open ran, at this block size's G, aligned, one workgroup per block
+        n = len(st)
+        assert log == [(LOG_OPEN, OPEN_G[bs], 1, 1, 2, 0, n, 0, 0, n)]
+    else:
+        assert log == []               # the composed route
     assert st == [0] * len(st)
     assert pt == data
     assert tail == bytes(64)           # nothing written past the end
@@ -143,7 +172,7 @@ def test_in_place(gpu, O, route, bs, total):
     assert st == [0] * len(st) and pt == data and tail == bytes(64)
 
 
-@pytest.mark.parametrize("bs,total", VARIANT_SHAPES)
+@pytest.mark.parametrize("bs,total", UNALIGNED_SHAPES)
 def test_unaligned_pointers(gpu, O, route, bs, total):
     torch = _torch()
     data, ct, refs = _case(bs, total)

@@ -104,6 +104,27 @@ def test_post_batch_vs_oracle(gpu, O, bs):
             assert ct[j * bs:j * bs + len(blk)] == c, (bs, total, j)
 
 
+LOG_PASS, LOG_QUAD, LOG_PASS_DC, LOG_WORDS = 1, 2, 3, 10   # include/glfsx.h
+
+
+def _launch_log_reset():
+    """Empties the launch log (glfsx_debug_pass_log), which is process-wide
+    and holds whatever earlier tests launched."""
+    from glfs_amd import _native as N
+    N.check(N.lib.glfsx_debug_pass_log(1, None, 0, None))
+
+
+def _launch_log():
+    """The records of the launch log (family, G, CHACHA, ALIGNED, ARX form,
+    ...) since _launch_log_reset; empties it."""
+    from glfs_amd import _native as N
+    buf = (ctypes.c_uint32 * (LOG_WORDS * 256))()
+    n = ctypes.c_size_t()
+    N.check(N.lib.glfsx_debug_pass_log(1, buf, 256, ctypes.byref(n)))
+    assert n.value <= 256
+    return [tuple(buf[i * LOG_WORDS:(i + 1) * LOG_WORDS]) for i in range(n.value)]
+
+
 @pytest.fixture
 def split_target():
     """Restores the split-mode target (include/glfsx.h) after a test."""
@@ -143,8 +164,18 @@ def test_arx_forms_vs_oracle(gpu, O, latency_wgs, split_target, bs, total):
         latency_wgs(thr)
         for target in (0, 2048):
             split_target(target)
+            _launch_log_reset()
             refs, ct = _post_batch_host(salt, data, bs)
             outs.append((refs, ct))
+            # the form the threshold asks for really ran: the asm forms 1 / 2
+            # in k_pass or k_pass_dc, or the compiler's form 0 (k_quad has
+            # no other) and never the one-launch post
+            log = _launch_log()
+            assert log, (thr, target)
+            if thr == 0:
+                assert all(r[0] in (LOG_PASS, LOG_PASS_DC) and r[4] in (1, 2) for r in log), log
+            else:
+                assert all(r[0] in (LOG_PASS, LOG_QUAD) and r[4] == 0 for r in log), log
             n0 = (total + bs - 1) // bs
             assert len(refs) == 64 * n0
             # read side (getF, batched): back to the plaintext
@@ -189,13 +220,18 @@ def test_fused_split_post_vs_oracle(gpu, O, latency_wgs, split_target, bs, total
     want = [O.post(salt, data[j * bs:(j + 1) * bs]) for j in range(n0)]
     for target in (2048, 1 << 31, 2048):
         split_target(target)
+        _launch_log_reset()
         refs, ct = _post_batch_host(salt, data, bs)
+        log = _launch_log()                 # one launch, and it is k_pass_dc
+        assert [r[0] for r in log] == [LOG_PASS_DC], (target, log)
         for j, (r, c) in enumerate(want):
             assert refs[64 * j:64 * j + 64] == r, (target, j)
             assert ct[j * bs:j * bs + len(c)] == c, (target, j)
     split_target(2048)
     ck = bytes(range(32))
+    _launch_log_reset()
     refs, _ = _post_batch_host(salt, data, bs, cid_key=ck)
+    assert [r[0] for r in _launch_log()] == [LOG_PASS_DC]
     for j in sorted({0, n0 - 1, rng.randrange(n0)}):
         assert refs[64 * j:64 * j + 64] == O.post(salt, data[j * bs:(j + 1) * bs],
                                                   cid_key=ck)[0], j

@@ -1,9 +1,9 @@
 """The units that need no GPU, as stand-alone programs built with the host
 compiler under AddressSanitizer and UBSan: the host runtime's DevicePool and
 job builders (glfs_amd/csrc/host.h, tests/c/host_units_test.cpp), and the
-launch layer's per-stream scratch and launch plans (stream_scratch.h,
-launch_plan.h; tests/c/stream_scratch_test.cpp, over a fake HIP runtime of
-its own).  Each runs as its own process: nothing is loaded into Python and no
+launch layer's per-stream scratch, launch plans and launch log
+(stream_scratch.h, launch_plan.h, launch_log.h;
+tests/c/stream_scratch_test.cpp, over a fake HIP runtime of its own).  Each runs as its own process: nothing is loaded into Python and no
 GPU call is made."""
 import os
 import shutil
@@ -21,7 +21,7 @@ def _build_and_run(tmp_path, name):
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")  # hipError_t, hipStream_t: the HIP headers
     out = str(tmp_path / name)
     subprocess.check_call(
-        [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
+        [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-pthread", "-fsanitize=address,undefined",
          "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
          "-isystem", os.path.join(rocm, "include"),
          "-I", os.path.join(ROOT, "glfs_amd", "csrc"),
