@@ -96,7 +96,7 @@ __device__ __forceinline__ uint32_t add3_a(uint32_t a, uint32_t b, uint32_t c) {
 // in compiler-visible C were 5.7% slower; that alternate is in git history).
 // The kernels take the form as their int template parameter A (0 = compiler-
 // scheduled C, 1 = asm in quarter-round order, 2 = asm step-interleaved);
-// the headline's CID pass runs form 1 (launch_g).
+// the headline's CID pass runs form 1 (launch_plan.h pass_rec).
 #define SB() __builtin_amdgcn_sched_barrier(0)
 constexpr int kCol[4][4] = {{0, 4, 8, 12}, {1, 5, 9, 13}, {2, 6, 10, 14}, {3, 7, 11, 15}};
 constexpr int kDia[4][4] = {{0, 5, 10, 15}, {1, 6, 11, 12}, {2, 7, 8, 13}, {3, 4, 9, 14}};

@@ -3,13 +3,12 @@
 // gfx950 kernels: post_kernels.hip (the launches, with its fragments b3_arx.h,
 // pass_kernels.h, quad_kernels.h, one_kernels.h, one_open_kernels.h,
 // small_kernels.h, ragged_kernels.h, read_kernels.h, open_kernels.h and
-// ragged_open_kernels.h
-// holding the kernels by family; ragged_groups.h the host form's grouping,
-// launch_plan.h the shape of a bulk launch and stream_scratch.h the
-// per-stream scratch its host half keeps, both free of device code),
-// tree_kernels.hip and
-// xof_kernels.hip (device_common.h: definitions the three share).  Not part
-// of the C-ABI.
+// ragged_open_kernels.h holding the kernels by family; ragged_groups.h the
+// host form's grouping, launch_plan.h every choice of kernel and launch shape
+// as pure functions that the host half obeys, launch_log.h the record of such
+// a choice, stream_scratch.h the per-stream scratch: free of device code),
+// tree_kernels.hip and xof_kernels.hip (device_common.h: definitions the
+// three share).  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -261,11 +260,11 @@ hipError_t launch_open_ragged(const OpenRaggedJob &, hipStream_t);
 hipError_t launch_fill(uint8_t *dst, uint64_t offset, uint64_t n, uint64_t seed,
                        hipStream_t s);
 
-// Split mode (post_kernels.hip launch_pass): a launch of fewer than `wgs`
+// Split mode (launch_plan.h pass_plan): a launch of fewer than `wgs`
 // workgroups spreads each message over up to 64 workgroups.  0 disables it.
 // Returns the previous value.
 uint32_t set_split_target(uint32_t wgs);
-// Latency-mode threshold in workgroups (see post_kernels.hip); returns the
+// Latency-mode threshold in workgroups (launch_plan.h Knobs); returns the
 // previous value.
 uint32_t set_latency_wgs(uint32_t wgs);
 // Drop all launch scratch kept for stream s on its device -- split mode,

@@ -15,9 +15,9 @@ namespace glfsx {
 // Kernel families of the bulk launches.
 enum : uint32_t { kLaunchPass = 1, kLaunchQuad = 2, kLaunchPassDc = 3, kLaunchOpen = 4 };
 
-// One launch, as the launch site passed it to the runtime: the template
-// arguments of the kernel and the grid.  kLaunchRecWords uint32_t, in this
-// order (include/glfsx.h documents it).
+// One launch: the template arguments of the kernel and the grid.  The
+// selection (launch_plan.h) returns it; the launch site runs and logs it.
+// kLaunchRecWords uint32_t, in this order (include/glfsx.h documents it).
 struct LaunchRec {
   uint32_t family;      // kLaunchPass ...
   uint32_t g;           // G; k_quad: quads per workgroup

@@ -563,8 +563,7 @@ constexpr int kStage = 4 * 512;
 //  - wait_ticks: that wait's bound in s_memrealtime ticks (100 MHz);
 //  - skip_msg: test hook -- the DEK of this message is written but its
 //    ready flag is not (~0u: none).
-constexpr uint32_t kLists = 8;           // one per XCD
-constexpr uint32_t kListStride = 32;     // words between counters (128 B)
+constexpr uint32_t kListStride = 32;  // words between counters (128 B); kLists: launch_plan.h
 struct DcConst {
   uint32_t *ready;
   uint32_t *lists;
@@ -584,21 +583,6 @@ struct DcState {
                       // run their CID pass as fine items (0: none)
   const DcConst *c;
 };
-
-// Items of work list x (kLists lists, message j on list j % kLists): all DEK
-// items of its m messages (2^sl each), then the CID items -- coarse (2^sl per
-// message) for its first m - F messages, fine (2^(sl+1) per message, half the
-// chunks per lane) for its last F.  The run-down at the end of a launch is
-// then made of items half as long.
-__host__ __device__ __forceinline__ uint32_t dc_list_msgs(uint32_t n, uint32_t x) {
-  return n > x ? (n - x + kLists - 1u) / kLists : 0u;
-}
-__host__ __device__ __forceinline__ uint32_t dc_list_fine(uint32_t m, uint32_t fine_div) {
-  return fine_div ? (m + fine_div - 1u) / fine_div : 0u;
-}
-__host__ __device__ __forceinline__ uint32_t dc_list_items(uint32_t m, uint32_t f, uint32_t sl) {
-  return (2u * m + f) << sl;
-}
 
 // The DEK pass stores message j's DEK with agent-scope atomic stores, waits
 // for them, then sets ready[j] = epoch; the CID workgroups of message j wait

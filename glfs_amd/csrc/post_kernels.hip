@@ -20,10 +20,10 @@
 //     ptext is read once per pass and ctext is never re-read.
 // Integer ALU work only (v_add3_u32 / v_xor_b32 / v_alignbit_b32); no MFMA.
 //
-// The host half below the fragments launches them.  The shape of a bulk
-// launch comes from launch_plan.h (pure functions); what a stream's launches
-// keep between them is one ScratchSlot per (device, stream) whose members
-// own their memory (stream_scratch.h).
+// The host half below the fragments builds the kernel arguments, asks
+// launch_plan.h (pure functions) which kernel runs with what shape, fetches
+// scratch and launches.  What a stream's launches keep between them is one
+// ScratchSlot per (device, stream) whose members own their memory.
 #include "kernels.h"
 
 #include <algorithm>
@@ -32,9 +32,9 @@
 #include <cstring>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "device_common.h"
-#include "launch_log.h"
 #include "launch_plan.h"
 #include "stream_scratch.h"
 
@@ -58,74 +58,46 @@ namespace {
 
 // The host side: launch plans and launches.
 
-// Latency mode: launches of at most this many 256-lane workgroups (default
-// 512 = 2 waves per SIMD) run the compiler-scheduled ARX form, and the CID
-// pass splits into a per-block keystream launch + a BLAKE3 pass.
-// glfsx_set_latency_wgs overrides it (tuning, tests of both forms).
-std::atomic<uint32_t> g_latency_wgs{512};
-uint32_t latency_wgs() { return g_latency_wgs.load(std::memory_order_relaxed); }
+// The tuning values (launch_plan.h: Knobs), read once per call.
+std::atomic<uint32_t> g_latency_wgs{512}, g_split_target{2048u};
+Knobs knobs() {
+  return {g_split_target.load(std::memory_order_relaxed),
+          g_latency_wgs.load(std::memory_order_relaxed)};
+}
 
 // The launch log (glfsx_debug_pass_log): off until first asked for; then
-// every bulk launch site below appends what it launched.  Never destroyed:
+// every bulk launch appends the record it was made from.  Never destroyed:
 // a launch on another thread may outlive the process's static destructors.
 LaunchLog &g_launch_log = *new LaunchLog();
-inline void log_launch(uint32_t family, int g, bool chacha, bool aligned, int form,
-                       uint32_t split_log2, uint32_t grid, uint64_t n, uint32_t fine_div = 0,
-                       uint64_t items = 0) {
-  if (!g_launch_log.on()) return;
-  g_launch_log.append(LaunchRec{family, uint32_t(g), chacha, aligned, uint32_t(form), split_log2,
-                                grid, fine_div, uint32_t(items), uint32_t(n)});
-}
 
-// From a runtime g to the template parameter G: f(integral_constant<int, G>)
-// for the one of Gs that g equals, hipErrorInvalidValue when it is none.  A
-// left fold: the kernels are instantiated, and so laid out in the code
-// object, in the order of Gs (a right fold reverses them).
-template <int... Gs, class F>
-hipError_t with_g(int g, F &&f) {
+// f(integral_constant<int, G>) for the G of Gs (a constexpr array of
+// launch_plan.h) that g equals, hipErrorInvalidValue when it is none.
+template <const auto &Gs, class F, size_t... I>
+hipError_t with_g(uint32_t g, F &&f, std::index_sequence<I...>) {
   hipError_t e = hipErrorInvalidValue;
-  (void)(... || (g == Gs && ((e = f(std::integral_constant<int, Gs>{})), true)));
+  (void)(... || (g == uint32_t(Gs[I]) && ((e = f(std::integral_constant<int, Gs[I]>{})), true)));
   return e;
 }
-
-// ARX form of the launches above the latency bound: the aligned CID pass
-// with no split and G >= 4 (the headline's) runs form 1 (quarter-round
-// order), everything else form 2 (step-interleaved; both one asm statement
-// per instruction).  Measured on one box, 2 interleaved reps: CID form 1
-// headline 992-995 vs 979-983 GiB/s with form 2, config 2 unchanged
-// (855-860); the DEK pass is indifferent.
-template <int G, bool CHACHA>
-hipError_t launch_g(const KArgs &a, bool aligned, hipStream_t s) {
-  const dim3 grid(uint32_t(a.n << a.split_log2)), block(256);
-  // <= 2 waves per SIMD (512 workgroups of 4 waves on 1024 SIMDs): the
-  // compiler-scheduled ARX issues faster than the asm form (tools/arx.hip)
-  const bool lat = grid.x <= latency_wgs();
-  if (aligned && lat) {
-    hipLaunchKernelGGL((k_pass<G, CHACHA, true, 0>), grid, block, 0, s, a);
-    log_launch(kLaunchPass, G, CHACHA, true, 0, a.split_log2, grid.x, a.n);
-  } else if (aligned) {
-    if constexpr (CHACHA) {
-      if (G >= 4 && a.split_log2 == 0) {
-        hipLaunchKernelGGL((k_pass<G, true, true, 1>), grid, block, 0, s, a);
-        log_launch(kLaunchPass, G, true, true, 1, a.split_log2, grid.x, a.n);
-        return hipGetLastError();
-      }
-    }
-    hipLaunchKernelGGL((k_pass<G, CHACHA, true, 2>), grid, block, 0, s, a);
-    log_launch(kLaunchPass, G, CHACHA, true, 2, a.split_log2, grid.x, a.n);
-  } else {
-    hipLaunchKernelGGL((k_pass<G, CHACHA, false, 2>), grid, block, 0, s, a);
-    log_launch(kLaunchPass, G, CHACHA, false, 2, a.split_log2, grid.x, a.n);
-  }
-  return hipGetLastError();
+template <const auto &Gs, class F>
+hipError_t with_g(uint32_t g, F &&f) {
+  return with_g<Gs>(g, f, std::make_index_sequence<std::size(Gs)>{});
 }
 
-// Split-mode target: workgroups per launch below which a message is spread
-// over more workgroups (fewer chunks per lane).  0 disables split mode
-// (glfsx_set_split_target: tests of both forms).
-std::atomic<uint32_t> g_split_target{2048u};
-PassPlan plan_for(uint64_t n, uint64_t maxlen) {
-  return pass_plan(n, maxlen, g_split_target.load(std::memory_order_relaxed), latency_wgs());
+// k_pass<G, CHACHA, ALIGNED, A> when that is r's instantiation and launchable.
+template <int G, bool CHACHA, bool ALIGNED, int A>
+bool try_pass(const LaunchRec &r, const KArgs &a, hipStream_t s) {
+  if constexpr (pass_form_ok(G, CHACHA, ALIGNED, A)) {
+    if (r.chacha == CHACHA && r.aligned == ALIGNED && r.form == A) {
+      hipLaunchKernelGGL((k_pass<G, CHACHA, ALIGNED, A>), dim3(r.grid), dim3(256), 0, s, a);
+      return true;
+    }
+  }
+  return false;
+}
+template <int G, bool CHACHA>
+bool try_pass_g(const LaunchRec &r, const KArgs &a, hipStream_t s) {
+  return try_pass<G, CHACHA, true, 0>(r, a, s) || try_pass<G, CHACHA, true, 1>(r, a, s) ||
+         try_pass<G, CHACHA, true, 2>(r, a, s) || try_pass<G, CHACHA, false, 2>(r, a, s);
 }
 
 // What the launches on one (device, stream) keep between them: launches on
@@ -135,6 +107,11 @@ PassPlan plan_for(uint64_t n, uint64_t maxlen) {
 // buffer only grows when a launch needs more; the old one is released after
 // its stream drains (StreamBuf::ensure).  Every member owns its memory, so
 // releasing a slot frees all of it.
+struct RagBufs {
+  StreamBuf plan;   // the plan's prefixes (RArgs::pre, wpre)
+  StreamBuf cv;     // chunk and group CVs (RArgs::cvs, gcv)
+  PinnedBlock tot;  // the plan's three totals
+};
 struct ScratchSlot {
   StreamBuf p;         // split mode: CVs, 32 B per workgroup
   StreamBuf cnt;       // split mode: arrival counters, 4 B per message, zero
@@ -147,13 +124,9 @@ struct ScratchSlot {
   DcConst dcc_host{};  // what was last copied there
   StreamBuf qctr;      // k_small_q: two banks of its item counter
   uint32_t qepoch = 0;
-  StreamBuf rplan;     // ragged post: the plan's prefixes (RArgs::pre, wpre)
-  StreamBuf rcv;       // ragged post: chunk and group CVs (RArgs::cvs, gcv)
-  PinnedBlock rtot;    // ragged post: the plan's three totals
+  RagBufs rag;         // ragged post (CVs of 32 B)
   StreamBuf open;      // verified read, composed route: digests, plaintext
-  StreamBuf oplan;     // ragged open: the plan's prefixes (RArgs::pre, wpre)
-  StreamBuf ocv;       // ragged open: chunk and group CVs, 64 B each
-  PinnedBlock otot;    // ragged open: the plan's three totals
+  RagBufs orag;        // ragged open (CVs of 64 B)
 };
 // g_scratch_mu guards the registry and every slot, and is held across a
 // getter's whole body, the drain of a growing buffer included: narrowing it
@@ -247,58 +220,31 @@ void dc_lists_zero(ScratchSlot *sl, hipStream_t s) {
   if (sl && sl->lists.p) (void)hipMemsetAsync(sl->lists.p, 0, kListWords * 4, s);
 }
 
-// A k_pass_dc launch failed after dc_get: its epoch was used without the
-// launch that clears the next bank.
-void dc_launch_failed(hipStream_t s) {
-  SlotLock g(s, false);
-  dc_lists_zero(g.sl, s);
-}
-
-hipError_t launch_quad(KArgs a, uint64_t maxlen, hipStream_t s) {
-  const int qpw = quad_qpw(maxlen);
-  const uint64_t kSpan = uint64_t(qpw) << 10;
-  const uint64_t W = maxlen > kSpan ? (maxlen + kSpan - 1) / kSpan : 1;
-  uint32_t sl = 0;
-  while ((1ull << sl) < W) ++sl;
-  a.split_log2 = sl;
+// The one launch-and-log site of k_pass and k_quad: r's instantiation over a,
+// with split-mode scratch when r splits.
+hipError_t launch_rec(const LaunchRec &r, KArgs a, hipStream_t s) {
+  if (!launchable(r)) return hipErrorInvalidValue;
+  a.split_log2 = r.split_log2;
   a.scratch = nullptr;
   a.cnt = nullptr;
-  if (sl) {
-    hipError_t e = scratch_get(&a, a.n << sl, a.n, s);
+  if (r.split_log2) {
+    hipError_t e = scratch_get(&a, r.grid, a.n, s);
     if (e != hipSuccess) return e;
   }
-  if (qpw == 64)
-    hipLaunchKernelGGL(k_quad<64>, dim3(uint32_t(a.n << sl)), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL(k_quad<256>, dim3(uint32_t(a.n << sl)), dim3(1024), 0, s, a);
-  log_launch(kLaunchQuad, qpw, false, true, 0, sl, uint32_t(a.n << sl), a.n);
+  hipError_t e = hipErrorInvalidValue;
+  if (r.family == kLaunchQuad)
+    e = with_g<kQuadQpws>(r.g, [&](auto Q) {
+      hipLaunchKernelGGL(k_quad<Q()>, dim3(r.grid), dim3(Q() == 64 ? 256 : 1024), 0, s, a);
+      return hipSuccess;
+    });
+  else if (r.family == kLaunchPass)
+    e = with_g<kPassGs>(r.g, [&](auto G) {
+      const bool ok = try_pass_g<G(), false>(r, a, s) || try_pass_g<G(), true>(r, a, s);
+      return ok ? hipSuccess : hipErrorInvalidValue;
+    });
+  if (e != hipSuccess) return e;
+  if (g_launch_log.on()) g_launch_log.append(r);
   return hipGetLastError();
-}
-
-bool quad_ok(const KArgs &a, uint64_t maxlen, bool aligned, uint32_t sl) {
-  const uint64_t chunks = a.n * (maxlen ? (maxlen + 1023) >> 10 : 1);
-  const bool refs4 = ((reinterpret_cast<uintptr_t>(a.refs) | a.out_off |
-                       a.ref_stride) & 3) == 0;
-  return aligned && refs4 && (a.n << sl) <= latency_wgs() &&
-         chunks <= 16384 && maxlen <= (64ull * 256) << 10;
-}
-
-template <bool CHACHA>
-hipError_t launch_pass(KArgs a, uint64_t maxlen, bool aligned,
-                       hipStream_t s) {
-  const auto [g, sl] = plan_for(a.n, maxlen);
-  if constexpr (!CHACHA) {
-    if (quad_ok(a, maxlen, aligned, sl)) return launch_quad(a, maxlen, s);
-  }
-  a.split_log2 = sl;
-  a.scratch = nullptr;
-  a.cnt = nullptr;
-  if (sl) {
-    hipError_t e = scratch_get(&a, a.n << sl, a.n, s);
-    if (e != hipSuccess) return e;
-  }
-  return with_g<1, 2, 4, 8, 16, 32, 64>(
-      g, [&](auto G) { return launch_g<G(), CHACHA>(a, aligned, s); });
 }
 
 // k_small_q's counter banks on stream s and this launch's epoch.
@@ -323,47 +269,26 @@ uint32_t resident_wgs(K k) {
   return uint32_t(std::max(per_cu, 1) * std::max(cus, 1));
 }
 
-// k_small_q hands out the last 1/kSmallFineDiv of the blobs as fine items.
-// 1 M x 4 KiB blobs, 3 interleaved reps: small blobs 911 / 919 / 926 GiB/s
-// at none / 1/4 / 1/8, config 4 end to end 780 / 791 / 801.
-constexpr uint32_t kSmallFineDiv = 8;
-
-template <int G, bool CHACHA, int A>
-hipError_t launch_small_q(const SArgs &a0, hipStream_t s) {
-  static const uint32_t slots = resident_wgs(k_small_q<G, CHACHA, A>);
-  uint32_t *ctr;
-  uint32_t epoch;
-  hipError_t e = small_q_get(s, &ctr, &epoch);
-  if (e != hipSuccess) return e;
-  SArgs a = a0;
-  const uint64_t fine = G > 1 ? a.n / kSmallFineDiv : 0;
-  a.n_coarse = (a.n - fine) >> 6;  // whole coarse items; the rest goes fine
-  const uint64_t rest = a.n - (a.n_coarse << 6), bpi = G > 1 ? 64 / G : 64;
-  const uint64_t items = a.n_coarse + (rest + bpi - 1) / bpi;
-  const uint64_t wgs = (items + 3) / 4;
-  const uint32_t grid = uint32_t(std::min<uint64_t>(wgs, slots ? slots : wgs));
-  hipLaunchKernelGGL((k_small_q<G, CHACHA, A>), dim3(grid), dim3(256), 0, s, a, ctr, epoch);
-  return hipGetLastError();
-}
-
+// One pass over the small blobs, as small_plan says: k_small, or k_small_q
+// with its counters and at most the resident workgroups.
 template <bool CHACHA>
-hipError_t launch_small_pass(const SArgs &a, uint64_t max_len, hipStream_t s) {
-  const uint64_t C = max_len ? (max_len + 1023) >> 10 : 1;
-  const dim3 grid(uint32_t((a.n + 255) / 256)), block(256);
-  const int gsel = C <= 1 ? 1 : C <= 2 ? 2 : C <= 4 ? 4 : C <= 8 ? 8 : C <= 16 ? 16 : 0;
-  if (grid.x <= latency_wgs())  // few blobs: the compiler's ARX form
-    return with_g<1, 2, 4, 8, 16>(gsel, [&](auto G) {
-      hipLaunchKernelGGL((k_small<G(), CHACHA, false>), grid, block, 0, s, a);
+hipError_t launch_small_pass(SArgs a, uint64_t max_len, hipStream_t s) {
+  const SmallPlan p = small_plan(a.n, max_len, CHACHA, knobs().latency_wgs);
+  a.n_coarse = p.n_coarse;
+  return with_g<kSmallGs>(uint32_t(p.g), [&](auto G) {
+    if (!p.queue) {
+      hipLaunchKernelGGL((k_small<G(), CHACHA, 0>), dim3(uint32_t(p.wgs)), dim3(256), 0, s, a);
       return hipGetLastError();
-    });
-  // more workgroups than the chip holds: per-wave items (k_small_q).  The
-  // CID pass runs ARX form 1 (quarter-round order), as the headline's CID
-  // pass: 928.8 vs 913.3 GiB/s small blobs, config 4 798.1 vs 787.3 (3
-  // interleaved reps, after the wave-offset fix; round 2 measured form 2
-  // ahead when half the waves took the per-lane path); the DEK pass form 2
-  constexpr int F = CHACHA ? 1 : 2;
-  return with_g<1, 2, 4, 8, 16>(
-      gsel, [&](auto G) { return launch_small_q<G(), CHACHA, F>(a, s); });
+    }
+    constexpr int A = CHACHA ? 1 : 2;  // small_plan's form
+    static const uint32_t slots = resident_wgs(k_small_q<G(), CHACHA, A>);
+    uint32_t *ctr, epoch;
+    hipError_t e = small_q_get(s, &ctr, &epoch);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_small_q<G(), CHACHA, A>), dim3(capped_grid(p.wgs, slots)), dim3(256), 0,
+                       s, a, ctr, epoch);
+    return hipGetLastError();
+  });
 }
 
 // The clock probe (g_clk): off until clock_probe is first called.
@@ -383,9 +308,13 @@ unsigned long long *clk_words() {
   return p;
 }
 
-KArgs make_args(const PostJob &job) {
+// The arguments of a pass over job under `key`, digests at out_off of each slot.
+KArgs pass_args(const PostJob &job, const uint32_t key[8], uint32_t base, uint32_t out_off) {
   KArgs a{};
   a.clk = clk_words();
+  for (int i = 0; i < 8; ++i) a.key[i] = key[i];
+  a.base = base;
+  a.out_off = out_off;
   a.src = job.src;
   a.ctext = job.ctext;
   a.stride = job.stride;
@@ -398,11 +327,98 @@ KArgs make_args(const PostJob &job) {
   return a;
 }
 
-bool is_aligned(const PostJob &job) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(job.src) |
-                      reinterpret_cast<uintptr_t>(job.ctext) |
-                      uintptr_t(job.stride);
-  return (x & 15) == 0;
+uint32_t low_bits(const void *p) { return uint32_t(reinterpret_cast<uintptr_t>(p)) & 15u; }
+
+PostShape shape_of(const PostJob &job, bool fuse = false) {
+  return {job.n,  job.msg_len, job.last_len, job.stride, low_bits(job.src), low_bits(job.ctext),
+          low_bits(job.out.refs), job.ctext != nullptr, job.out.bf, job.out.stride, fuse};
+}
+
+KArgs dek_args(const PostJob &job, uint32_t out_off) {
+  return pass_args(job, job.salt, kKeyed, out_off);
+}
+KArgs cid_args(const PostJob &job) {
+  return pass_args(job, job.cid_key, job.cid_keyed ? kKeyed : 0u, 0);
+}
+
+// launch_decrypt at a latency bound already read.
+hipError_t decrypt_with(const uint8_t *ctext, uint8_t *ptext, uint64_t n, uint64_t bs,
+                        uint64_t last_len, const uint8_t *refs, uint32_t latency_wgs,
+                        hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (bs % 64) return hipErrorInvalidValue;
+  KArgs a{};
+  a.src = ctext;
+  a.ctext = ptext;
+  a.msg_len = bs;
+  a.last_len = last_len;
+  a.n = n;
+  a.refs = const_cast<uint8_t *>(refs);
+  const DecryptPlan p =
+      decrypt_plan(n, bs, last_len, ((low_bits(ctext) | low_bits(ptext)) & 15) == 0, latency_wgs);
+  if (p.units) {
+    if (p.lines.form == 0)
+      hipLaunchKernelGGL(k_decrypt_lines<0>, dim3(p.lines.grid), dim3(256), 0, s, a, p.units,
+                         p.upb_shift, p.run_shift);
+    else
+      hipLaunchKernelGGL(k_decrypt_lines<2>, dim3(p.lines.grid), dim3(256), 0, s, a, p.units,
+                         p.upb_shift, p.run_shift);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (!p.grid) return hipSuccess;
+  a.stride = p.first_kb;  // first keystream block left for k_decrypt
+  hipLaunchKernelGGL(k_decrypt, dim3(p.grid), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// The CID side as cid_route says: the one k_pass launch, or the keystream
+// launch and a BLAKE3 pass over the ctext.
+hipError_t launch_cid(const PostJob &job, const CidRoute &c, uint32_t latency_wgs, hipStream_t s) {
+  KArgs a = cid_args(job);
+  if (c.keystream) {
+    hipError_t e = decrypt_with(job.src, job.ctext, job.n, c.ks_bs, job.last_len, job.out.refs,
+                                latency_wgs, s);
+    if (e != hipSuccess) return e;
+    a.src = job.ctext;
+    a.ctext = nullptr;
+  }
+  return launch_rec(c.pass, a, s);
+}
+
+// The one launch-and-log site of k_pass_dc: post_route's fused record r.
+hipError_t launch_dc(const LaunchRec &r, const PostJob &job, hipStream_t s) {
+  if (r.family != kLaunchPassDc || !launchable(r)) return hipErrorInvalidValue;
+  const uint32_t sl = r.split_log2;
+  const uint64_t wgs = job.n << sl;
+  KArgs a = dek_args(job, 32);
+  a.split_log2 = sl;
+  // scratch: DEK CVs (wgs), coarse CID CVs (wgs), fine CID CVs (2 wgs)
+  hipError_t e = scratch_get(&a, 4 * wgs, 2 * job.n, s);
+  if (e != hipSuccess) return e;
+  DcState d{};
+  e = dc_get(job.n, s, &d);
+  if (e != hipSuccess) return e;
+  d.n = r.n;
+  d.sl = sl;
+  d.fine_div = r.fine_div;
+  KArgs b = cid_args(job);
+  b.split_log2 = sl;
+  b.scratch = a.scratch + wgs * 8;
+  b.cnt = a.cnt + job.n;
+  KArgs c = b;  // fine CID items: twice the workgroups per message
+  c.split_log2 = sl + 1;
+  c.scratch = b.scratch + wgs * 8;
+  e = with_g<kDcGs>(r.g, [&](auto G) {
+    hipLaunchKernelGGL(k_pass_dc<G()>, dim3(r.grid), dim3(256), 0, s, a, b, c, d);
+    if (g_launch_log.on()) g_launch_log.append(r);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess) {  // the epoch was used without the launch that clears the next bank
+    SlotLock g(s, false);
+    dc_lists_zero(g.sl, s);
+  }
+  return e;
 }
 
 }  // namespace
@@ -447,134 +463,36 @@ void blake3_iv_words(uint32_t w[8]) {
   for (int i = 0; i < 8; ++i) w[i] = kIV[i];
 }
 
-hipError_t launch_keyed_hash(const PostJob &job, uint32_t out_off,
-                             hipStream_t s) {
+hipError_t launch_keyed_hash(const PostJob &job, uint32_t out_off, hipStream_t s) {
   if (job.n == 0) return hipSuccess;
-  KArgs a = make_args(job);
-  for (int i = 0; i < 8; ++i) a.key[i] = job.salt[i];
-  a.base = kKeyed;
-  a.out_off = out_off;
-  const uint64_t maxlen = job.n > 1 ? std::max(job.msg_len, job.last_len)
-                                    : job.last_len;
-  return launch_pass<false>(a, maxlen, is_aligned(job), s);
-}
-
-// The fine-item share of k_pass_dc's CID items: the last ceil(m / 4)
-// messages of each work list.
-constexpr uint32_t kDcFineDiv = 4;
-
-// Split-mode post of many-wave size in one launch (k_pass_dc): both passes
-// of launch_keyed_hash + launch_cid_pass when each would be one k_pass<G,
-// CHACHA, true, 2> launch with the same plan.
-hipError_t launch_post_fused(const PostJob &job, hipStream_t s, bool *done) {
-  *done = false;
-  if (job.n < 2 || !is_aligned(job)) return hipSuccess;
-  if ((reinterpret_cast<uintptr_t>(job.out.refs) | job.out.stride) & 3) return hipSuccess;
-  const uint64_t maxlen = std::max(job.msg_len, job.last_len);
-  const PassPlan plan = plan_for(job.n, maxlen);
-  const int g = plan.g;
-  const uint32_t sl = plan.sl;
-  const uint64_t wgs = job.n << sl;
-  // launches of 320-512 workgroups (default threshold) also run fused in the
-  // many-wave form: Create of 96 / 128 MiB at 1 MiB blocks (384 / 512
-  // workgroups) 359 -> 368 / 451 -> 487 GiB/s, 80 MiB a tie, 64 MiB (256)
-  // 6 % slower, so it stays in latency mode (scripts/lat_thr.py)
-  if (sl == 0 || wgs * 8 <= uint64_t(latency_wgs()) * 5 || (g != 1 && g != 2 && g != 4))
-    return hipSuccess;
-  const uint64_t chunks = job.n * ((maxlen + 1023) >> 10);
-  KArgs a = make_args(job);
-  for (int i = 0; i < 8; ++i) a.key[i] = job.salt[i];
-  a.base = kKeyed;
-  a.out_off = 32;
-  if (quad_ok(a, maxlen, true, sl) || chunks == 0) return hipSuccess;
-  a.split_log2 = sl;
-  // scratch: DEK CVs (wgs), coarse CID CVs (wgs), fine CID CVs (2 wgs)
-  hipError_t e = scratch_get(&a, 4 * wgs, 2 * job.n, s);
-  if (e != hipSuccess) return e;
-  DcState d{};
-  e = dc_get(job.n, s, &d);
-  if (e != hipSuccess) return e;
-  d.n = uint32_t(job.n);
-  d.sl = sl;
-  d.fine_div = (g > 1 && sl < kMaxSplitLog2) ? kDcFineDiv : 0u;
-  KArgs b = a;
-  for (int i = 0; i < 8; ++i) b.key[i] = job.cid_key[i];
-  b.base = job.cid_keyed ? kKeyed : 0u;
-  b.out_off = 0;
-  b.scratch = a.scratch + wgs * 8;
-  b.cnt = a.cnt + job.n;
-  KArgs c = b;  // fine CID items: twice the workgroups per message
-  c.split_log2 = sl + 1;
-  c.scratch = b.scratch + wgs * 8;
-  uint64_t items = 0;
-  for (uint32_t x = 0; x < kLists; ++x) {
-    const uint32_t m = dc_list_msgs(d.n, x);
-    items += dc_list_items(m, dc_list_fine(m, d.fine_div), sl);
-  }
-  const dim3 grid{uint32_t(items)}, block{256};
-  e = with_g<1, 2, 4>(g, [&](auto G) {
-    hipLaunchKernelGGL(k_pass_dc<G()>, grid, block, 0, s, a, b, c, d);
-    log_launch(kLaunchPassDc, G(), true, true, 2, sl, grid.x, job.n, d.fine_div, items);
-    return hipGetLastError();
-  });
-  *done = true;
-  if (e != hipSuccess) dc_launch_failed(s);
-  return e;
+  const Knobs k = knobs();
+  const PostShape j = shape_of(job);
+  return launch_rec(dek_rec(j, plan_of(j, k), out_off, k), dek_args(job, out_off), s);
 }
 
 hipError_t launch_post(const PostJob &job, hipStream_t s, bool fused) {
   if (job.n == 0) return hipSuccess;
-  bool done = false;
-  hipError_t e = fused ? launch_post_fused(job, s, &done) : hipSuccess;
-  if (e != hipSuccess || done) return e;
-  e = launch_keyed_hash(job, 32, s);
+  const Knobs k = knobs();
+  const PostRoute r = post_route(shape_of(job, fused), k);
+  if (r.fused) return launch_dc(r.dek, job, s);
+  hipError_t e = launch_rec(r.dek, dek_args(job, 32), s);
   if (e != hipSuccess) return e;
-  return launch_cid_pass(job, s);
+  return launch_cid(job, r.cid, k.latency_wgs, s);
 }
 
 hipError_t launch_cid_pass(const PostJob &job, hipStream_t s) {
   if (job.n == 0) return hipSuccess;
-  KArgs a = make_args(job);
-  for (int i = 0; i < 8; ++i) a.key[i] = job.cid_key[i];
-  a.base = job.cid_keyed ? kKeyed : 0u;
-  a.out_off = 0;
-  const uint64_t maxlen = job.n > 1 ? std::max(job.msg_len, job.last_len)
-                                    : job.last_len;
-  const uint32_t sl = plan_for(job.n, maxlen).sl;
-  // Latency-bound launches (index nodes, single posts, small batches): the
-  // fused pass leaves one wave per SIMD running ChaCha20 and BLAKE3 in
-  // series.  The keystream has no chaining, so instead every 64-B block gets
-  // its own lane (the read side's kernels: ctext = ptext ^ ChaCha20(DEK_j)),
-  // and the CID is a BLAKE3 pass over the ctext like the DEK pass.  Needs
-  // the ctext in memory, DEKs in dense slots, contiguous messages.
-  const bool dense = job.out.bf >= job.n;
-  const bool contiguous = job.n == 1 || job.stride == job.msg_len;
-  if ((job.n << sl) <= latency_wgs() && job.ctext && dense && contiguous &&
-      (job.n == 1 || job.msg_len % 64 == 0)) {
-    const uint64_t bs = job.n > 1 ? job.msg_len
-                                  : std::max<uint64_t>(4096, (job.last_len + 4095) & ~4095ull);
-    hipError_t e = launch_decrypt(job.src, job.ctext, job.n, bs, job.last_len,
-                                  job.out.refs, s);
-    if (e != hipSuccess) return e;
-    KArgs b = a;
-    b.src = job.ctext;
-    b.ctext = nullptr;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(job.ctext) |
-                           uintptr_t(job.stride)) & 15) == 0;
-    return launch_pass<false>(b, maxlen, aligned, s);
-  }
-  return launch_pass<true>(a, maxlen, is_aligned(job), s);
+  const Knobs k = knobs();
+  const PostShape j = shape_of(job);
+  return launch_cid(job, cid_route(j, plan_of(j, k), k), k.latency_wgs, s);
 }
 
 hipError_t launch_fill(uint8_t *dst, uint64_t offset, uint64_t n, uint64_t seed,
                        hipStream_t s) {
   if (n == 0) return hipSuccess;
   if (offset & 7) return hipErrorInvalidValue;
-  const uint64_t words = (n + 7) >> 3;
-  uint64_t grid = (words + 255) / 256;
-  if (grid > 65536) grid = 65536;
-  hipLaunchKernelGGL(k_fill, dim3(uint32_t(grid)), dim3(256), 0, s, dst, offset,
-                     n, seed);
+  const uint32_t grid = capped_grid((((n + 7) >> 3) + 255) / 256, 65536);
+  hipLaunchKernelGGL(k_fill, dim3(grid), dim3(256), 0, s, dst, offset, n, seed);
   return hipGetLastError();
 }
 
@@ -619,35 +537,47 @@ hipError_t launch_post_small(const SmallJob &job, hipStream_t s) {
 // 1 MiB and grow with a quarter of headroom.
 constexpr size_t kGrowFloor = size_t(1) << 20;
 
-// The ragged post's buffers on stream s: `plan` / `cv` bytes (0: leave that
-// one alone) and the pinned words for the plan's totals.
-static hipError_t rag_get(hipStream_t s, size_t plan, size_t cv, uint8_t **d_plan,
-                          uint8_t **d_cv, uint64_t **tot, uint64_t **d_tot) {
-  SlotLock g(s);
-  if (g.sd.e != hipSuccess) return g.sd.e;
-  hipError_t e = g.sl->rtot.ensure();
+// The plan of a ragged call over a (src, offs, lens, n, lo, hi set) in the
+// post's or the open's buffers: count, prefix, the totals (chunks, merge
+// groups, messages of more than 256 chunks), CV scratch of cv_words words per
+// chunk and group.  MARK: a message not selected gets status `mark` in unsel.
+template <bool MARK>
+static hipError_t rag_plan(RArgs &a, RagBufs ScratchSlot::*set, uint32_t cv_words, uint32_t *unsel,
+                           uint32_t mark, uint64_t totals[3], hipStream_t s) {
+  a.m = (a.n + kRagWG - 1) / kRagWG;
+  uint64_t *tot = nullptr, *d_tot = nullptr;
+  // `plan` / `cv` bytes (0: leave that one alone) and the pinned totals
+  auto get = [&](size_t plan, size_t cv) {
+    SlotLock g(s);
+    if (g.sd.e != hipSuccess) return g.sd.e;
+    RagBufs &b = g.sl->*set;
+    hipError_t e = b.tot.ensure();
+    if (e == hipSuccess) e = b.plan.ensure(s, plan, kGrowFloor, 4, false);
+    if (e == hipSuccess) e = b.cv.ensure(s, cv, kGrowFloor, 4, false);
+    a.pre = b.plan.as<uint64_t>();
+    a.wpre = a.pre + a.n;
+    if (cv) a.cvs = b.cv.as<uint32_t>();
+    tot = static_cast<uint64_t *>(b.tot.h);
+    d_tot = static_cast<uint64_t *>(b.tot.d);
+    return e;
+  };
+  hipError_t e = get(8 * (a.n + 3 * (a.m + 1)), 0);
   if (e != hipSuccess) return e;
-  e = g.sl->rplan.ensure(s, plan, kGrowFloor, 4, false);
+  hipLaunchKernelGGL(k_rag_count<MARK>, dim3(uint32_t(a.m)), dim3(kRagWG), 0, s, a, unsel, mark);
+  e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = g.sl->rcv.ensure(s, cv, kGrowFloor, 4, false);
+  hipLaunchKernelGGL(k_rag_prefix<1024>, dim3(3), dim3(1024), 0, s, a.wpre, a.m, d_tot);
+  e = hipGetLastError();
   if (e != hipSuccess) return e;
-  *d_plan = g.sl->rplan.as<uint8_t>();
-  *d_cv = g.sl->rcv.as<uint8_t>();
-  *tot = static_cast<uint64_t *>(g.sl->rtot.h);
-  *d_tot = static_cast<uint64_t *>(g.sl->rtot.d);
-  return hipSuccess;
-}
-
-template <bool CHACHA>
-static hipError_t launch_rag_chunk(const RArgs &a, hipStream_t s) {
-  const uint64_t tiles = (a.total + 255) >> 8;
-  const dim3 grid(uint32_t(std::min<uint64_t>(tiles, 1u << 20))), block(256);
-  // few tiles: the compiler's ARX form, as launch_g
-  if (tiles <= latency_wgs())
-    hipLaunchKernelGGL((k_rag_chunk<CHACHA, 0>), grid, block, 0, s, a);
-  else
-    hipLaunchKernelGGL((k_rag_chunk<CHACHA, 2>), grid, block, 0, s, a);
-  return hipGetLastError();
+  // the one host wait of the call: the totals size the CV scratch and the
+  // launches that follow
+  e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return e;
+  for (int i = 0; i < 3; ++i) totals[i] = __atomic_load_n(tot + i, __ATOMIC_RELAXED);
+  if (totals[0] == 0) return hipSuccess;  // nothing selected
+  e = get(0, 4 * size_t(cv_words) * (totals[0] + totals[1]));
+  a.gcv = a.cvs + cv_words * totals[0];
+  return e;
 }
 
 // One pass of the ragged post: the chunks, then the merge levels that have
@@ -655,21 +585,19 @@ static hipError_t launch_rag_chunk(const RArgs &a, hipStream_t s) {
 template <bool CHACHA>
 static hipError_t launch_rag_pass(RArgs a, const uint64_t tot[3], hipStream_t s) {
   a.total = tot[0];
-  hipError_t e = launch_rag_chunk<CHACHA>(a, s);
-  if (e != hipSuccess) return e;
-  if (tot[1]) {
-    a.total = tot[1];
-    hipLaunchKernelGGL(k_rag_merge_a, dim3(uint32_t(std::min<uint64_t>(tot[1], 1u << 20))),
-                       dim3(256), 0, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  if (tot[2]) {
-    a.total = tot[2];
-    hipLaunchKernelGGL(k_rag_merge_b, dim3(uint32_t(std::min<uint64_t>(tot[2], 1u << 20))),
-                       dim3(256), 0, s, a);
-    e = hipGetLastError();
-  }
+  const GridForm p = rag_chunk_plan(tot[0], knobs().latency_wgs);
+  if (p.form == 0)
+    hipLaunchKernelGGL((k_rag_chunk<CHACHA, 0>), dim3(p.grid), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((k_rag_chunk<CHACHA, 2>), dim3(p.grid), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  auto merge = [&](auto k, uint64_t total) {  // a level that has work
+    a.total = total;
+    hipLaunchKernelGGL(k, dim3(capped_grid(total, 1u << 20)), dim3(256), 0, s, a);
+    return hipGetLastError();
+  };
+  if (e == hipSuccess && tot[1]) e = merge(k_rag_merge_a, tot[1]);
+  if (e == hipSuccess && tot[2]) e = merge(k_rag_merge_b, tot[2]);
   return e;
 }
 
@@ -685,32 +613,9 @@ hipError_t launch_post_ragged(const RaggedJob &job, hipStream_t s) {
   a.lo = job.lo;
   a.hi = job.hi;
   a.refs = job.refs;
-  a.m = (job.n + kRagWG - 1) / kRagWG;
-  uint8_t *d_plan, *d_cv;
-  uint64_t *tot, *d_tot;
-  hipError_t e = rag_get(s, 8 * (job.n + 3 * (a.m + 1)), 0, &d_plan, &d_cv, &tot, &d_tot);
-  if (e != hipSuccess) return e;
-  a.pre = reinterpret_cast<uint64_t *>(d_plan);
-  a.wpre = a.pre + job.n;
-  hipLaunchKernelGGL(k_rag_count<false>, dim3(uint32_t(a.m)), dim3(kRagWG), 0, s, a,
-                     static_cast<uint32_t *>(nullptr), 0u);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_rag_prefix<1024>, dim3(3), dim3(1024), 0, s, a.wpre, a.m, d_tot);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  // the one host wait of the call: the totals size the CV scratch and the
-  // launches below
-  e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return e;
-  const uint64_t totals[3] = {__atomic_load_n(tot + 0, __ATOMIC_RELAXED),
-                              __atomic_load_n(tot + 1, __ATOMIC_RELAXED),
-                              __atomic_load_n(tot + 2, __ATOMIC_RELAXED)};
-  if (totals[0] == 0) return hipSuccess;  // nothing selected
-  e = rag_get(s, 0, 32 * (totals[0] + totals[1]), &d_plan, &d_cv, &tot, &d_tot);
-  if (e != hipSuccess) return e;
-  a.cvs = reinterpret_cast<uint32_t *>(d_cv);
-  a.gcv = a.cvs + 8 * totals[0];
+  uint64_t totals[3];
+  hipError_t e = rag_plan<false>(a, &ScratchSlot::rag, 8, nullptr, 0u, totals, s);
+  if (e != hipSuccess || totals[0] == 0) return e;
   for (int i = 0; i < 8; ++i) a.key[i] = job.salt[i];
   a.base = kKeyed;
   a.out_off = 32;
@@ -760,139 +665,67 @@ hipError_t debug_wgtime(uint64_t *out) {
 }
 #endif
 
-hipError_t launch_med(const OneDesc *descs, uint32_t n, uint64_t max_len,
-                      hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  if (max_len > kMaxMedLen || max_len <= kMaxOneLen) return hipErrorInvalidValue;
-  const uint32_t wmax = uint32_t((max_len + 65535) >> 16);
-  hipLaunchKernelGGL(k_med_dek, dim3(n * wmax), dim3(256), 0, s, descs, wmax);
+// k_med_dek then k_med_cid (or their _v forms) over n messages of at most
+// len bytes, a workgroup per 64 KiB.
+template <class K, class A>
+static hipError_t med_launch(K dek, K cid, uint32_t n, uint64_t len, const A &a, hipStream_t s) {
+  if (len > kMaxMedLen || len <= kMaxOneLen) return hipErrorInvalidValue;
+  const uint32_t wmax = uint32_t((len + 65535) >> 16);
+  hipLaunchKernelGGL(dek, dim3(n * wmax), dim3(256), 0, s, a, wmax);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_med_cid, dim3(n * wmax), dim3(256), 0, s, descs, wmax);
+  hipLaunchKernelGGL(cid, dim3(n * wmax), dim3(256), 0, s, a, wmax);
   return hipGetLastError();
 }
-
-hipError_t launch_one(const OneDesc *descs, uint32_t n, uint64_t max_len,
-                      hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  if (max_len > kMaxOneLen) return hipErrorInvalidValue;
-  if (max_len <= 16 * 1024)
-    hipLaunchKernelGGL(k_one<16>, dim3(n), dim3(64), 0, s, descs);
-  else
-    hipLaunchKernelGGL(k_one<64>, dim3(n), dim3(256), 0, s, descs);
-  return hipGetLastError();
+hipError_t launch_med(const OneDesc *descs, uint32_t n, uint64_t max_len, hipStream_t s) {
+  return n ? med_launch(k_med_dek, k_med_cid, n, max_len, descs, s) : hipSuccess;
 }
-
 hipError_t launch_med_v(const OneDesc &d, hipStream_t s) {
-  if (d.len > kMaxMedLen || d.len <= kMaxOneLen) return hipErrorInvalidValue;
-  const uint32_t wmax = uint32_t((uint64_t(d.len) + 65535) >> 16);
-  hipLaunchKernelGGL(k_med_dek_v, dim3(wmax), dim3(256), 0, s, d, wmax);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_med_cid_v, dim3(wmax), dim3(256), 0, s, d, wmax);
-  return hipGetLastError();
+  return med_launch(k_med_dek_v, k_med_cid_v, 1, d.len, d, s);
 }
 
-hipError_t launch_one_v(const OneDesc &d, hipStream_t s) {
-  if (d.len > kMaxOneLen) return hipErrorInvalidValue;
-  if (d.len <= 16 * 1024)
-    hipLaunchKernelGGL(k_one_v<16>, dim3(1), dim3(64), 0, s, d);
+// k_one (or k_one_v): 16 chunks a workgroup of 64 lanes up to 16 KiB, else 64 of 256.
+template <class K, class A>
+static hipError_t one_launch(K k16, K k64, uint32_t n, uint64_t len, const A &a, hipStream_t s) {
+  if (len > kMaxOneLen) return hipErrorInvalidValue;
+  if (len <= 16 * 1024)
+    hipLaunchKernelGGL(k16, dim3(n), dim3(64), 0, s, a);
   else
-    hipLaunchKernelGGL(k_one_v<64>, dim3(1), dim3(256), 0, s, d);
+    hipLaunchKernelGGL(k64, dim3(n), dim3(256), 0, s, a);
   return hipGetLastError();
 }
-
-// k_one_open's workgroup: four lanes per quad, two trees when salted.
-template <int QUADS, bool SALTED>
-constexpr uint32_t one_open_lanes() {
-  return QUADS * (SALTED ? 8 : 4);
+hipError_t launch_one(const OneDesc *descs, uint32_t n, uint64_t max_len, hipStream_t s) {
+  return n ? one_launch(k_one<16>, k_one<64>, n, max_len, descs, s) : hipSuccess;
+}
+hipError_t launch_one_v(const OneDesc &d, hipStream_t s) {
+  return one_launch(k_one_v<16>, k_one_v<64>, 1, d.len, d, s);
 }
 
+// k_one_open (or _v): 16 quads up to 16 KiB, else 64; four lanes per quad,
+// two trees when salted.
+template <class K, class A>
+static hipError_t one_open_launch(K k16s, K k64s, K k16, K k64, uint32_t n, uint64_t len,
+                                  bool salted, const A &a, hipStream_t s) {
+  if (len > kMaxOneLen) return hipErrorInvalidValue;
+  const bool small = len <= 16 * 1024;
+  const K k = salted ? (small ? k16s : k64s) : (small ? k16 : k64);
+  hipLaunchKernelGGL(k, dim3(n), dim3((small ? 16 : 64) * (salted ? 8 : 4)), 0, s, a);
+  return hipGetLastError();
+}
 hipError_t launch_one_open(const OneOpenDesc *descs, uint32_t n, uint64_t max_len, bool salted,
                            hipStream_t s) {
   if (n == 0) return hipSuccess;
-  if (max_len > kMaxOneLen) return hipErrorInvalidValue;
-  const bool small = max_len <= 16 * 1024;
-  if (salted && small)
-    hipLaunchKernelGGL((k_one_open<16, true>), dim3(n), dim3(one_open_lanes<16, true>()), 0, s,
-                       descs);
-  else if (salted)
-    hipLaunchKernelGGL((k_one_open<64, true>), dim3(n), dim3(one_open_lanes<64, true>()), 0, s,
-                       descs);
-  else if (small)
-    hipLaunchKernelGGL((k_one_open<16, false>), dim3(n), dim3(one_open_lanes<16, false>()), 0, s,
-                       descs);
-  else
-    hipLaunchKernelGGL((k_one_open<64, false>), dim3(n), dim3(one_open_lanes<64, false>()), 0, s,
-                       descs);
-  return hipGetLastError();
+  return one_open_launch(k_one_open<16, true>, k_one_open<64, true>, k_one_open<16, false>,
+                         k_one_open<64, false>, n, max_len, salted, descs, s);
 }
-
 hipError_t launch_one_open_v(const OneOpenDesc &d, bool salted, hipStream_t s) {
-  if (d.len > kMaxOneLen) return hipErrorInvalidValue;
-  const bool small = d.len <= 16 * 1024;
-  if (salted && small)
-    hipLaunchKernelGGL((k_one_open_v<16, true>), dim3(1), dim3(one_open_lanes<16, true>()), 0, s,
-                       d);
-  else if (salted)
-    hipLaunchKernelGGL((k_one_open_v<64, true>), dim3(1), dim3(one_open_lanes<64, true>()), 0, s,
-                       d);
-  else if (small)
-    hipLaunchKernelGGL((k_one_open_v<16, false>), dim3(1), dim3(one_open_lanes<16, false>()), 0,
-                       s, d);
-  else
-    hipLaunchKernelGGL((k_one_open_v<64, false>), dim3(1), dim3(one_open_lanes<64, false>()), 0,
-                       s, d);
-  return hipGetLastError();
+  return one_open_launch(k_one_open_v<16, true>, k_one_open_v<64, true>, k_one_open_v<16, false>,
+                         k_one_open_v<64, false>, 1, d.len, salted, d, s);
 }
 
-hipError_t launch_decrypt(const uint8_t *ctext, uint8_t *ptext, uint64_t n,
-                          uint64_t bs, uint64_t last_len, const uint8_t *refs,
-                          hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  if (bs % 64) return hipErrorInvalidValue;
-  KArgs a{};
-  a.src = ctext;
-  a.ctext = ptext;
-  a.msg_len = bs;
-  a.last_len = last_len;
-  a.n = n;
-  a.refs = const_cast<uint8_t *>(refs);
-  const uint64_t total = (n - 1) * bs + last_len;
-  const uint64_t kbs = (total + 63) >> 6;
-  // bulk: whole 4 KiB units through the line kernel (uniform DEK per unit)
-  uint64_t units = 0;
-  if (bs % 4096 == 0 && ((reinterpret_cast<uintptr_t>(ctext) |
-                          reinterpret_cast<uintptr_t>(ptext)) & 15) == 0)
-    units = total >> 12;
-  if (units) {
-    const uint64_t upb = bs >> 12;
-    const uint32_t upb_shift =
-        (upb & (upb - 1)) == 0 ? uint32_t(__builtin_ctzll(upb)) : 64u;
-    // runs of 2^run_shift units per wave (inside one block), as long as
-    // there are still >= 65536 runs: the grid (<= 16384 workgroups of 4
-    // waves) stays as fine-grained as with one unit per step
-    uint32_t run_shift = 0;
-    if (upb_shift < 64)
-      while (run_shift < upb_shift && (units >> (run_shift + 1)) >= 65536) ++run_shift;
-    const uint64_t runs = (units + (1ull << run_shift) - 1) >> run_shift;
-    uint64_t grid = (runs + 3) / 4;
-    if (grid > 16384) grid = 16384;
-    if (grid <= latency_wgs())
-      hipLaunchKernelGGL(k_decrypt_lines<0>, dim3(uint32_t(grid)), dim3(256), 0, s,
-                         a, units, upb_shift, run_shift);
-    else
-      hipLaunchKernelGGL(k_decrypt_lines<2>, dim3(uint32_t(grid)), dim3(256), 0, s,
-                         a, units, upb_shift, run_shift);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  a.stride = units << 6;  // first keystream block left for k_decrypt
-  if (a.stride >= kbs) return hipSuccess;
-  uint64_t grid = (kbs - a.stride + 255) / 256;
-  if (grid > 65536) grid = 65536;
-  hipLaunchKernelGGL(k_decrypt, dim3(uint32_t(grid)), dim3(256), 0, s, a);
-  return hipGetLastError();
+hipError_t launch_decrypt(const uint8_t *ctext, uint8_t *ptext, uint64_t n, uint64_t bs,
+                          uint64_t last_len, const uint8_t *refs, hipStream_t s) {
+  return decrypt_with(ctext, ptext, n, bs, last_len, refs, knobs().latency_wgs, s);
 }
 
 hipError_t launch_chacha_xor(const uint32_t k[8], const uint8_t *src,
@@ -903,10 +736,8 @@ hipError_t launch_chacha_xor(const uint32_t k[8], const uint8_t *src,
   a.ctext = dst;
   a.msg_len = n;
   for (int i = 0; i < 8; ++i) a.key[i] = k[i];
-  const uint64_t nblk = (n + 63) >> 6;
-  uint64_t grid = (nblk + 255) / 256;
-  if (grid > 65536) grid = 65536;
-  hipLaunchKernelGGL(k_chacha_xor, dim3(uint32_t(grid)), dim3(256), 0, s, a);
+  const uint32_t grid = capped_grid((((n + 63) >> 6) + 255) / 256, 65536);
+  hipLaunchKernelGGL(k_chacha_xor, dim3(grid), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
@@ -920,19 +751,6 @@ int set_open_route(int route) {
   return g_open_route.exchange(route, std::memory_order_relaxed);
 }
 
-// Where auto takes the fused route: only at shapes whose neighbours in the
-// sweep of scripts/open_rate.py had k_open's median at or above the composed
-// route's in the same run (profiles/open/open_rate.json, DESIGN.md "k_open --
-// the verified read").  From 1024 blocks on (one workgroup per block then
-// fills every CU's four slots; at 512 the two routes tie and at 256 the
-// composed one wins by a fifth), blocks of at least 256 KiB (at 64 KiB only
-// one wave of a workgroup has chunks: 0.84 of composed), and 1 GiB in all
-// (the smallest total measured at each block size).
-constexpr uint64_t kOpenFusedMinBlocks = 1024;
-constexpr uint64_t kOpenFusedMinBs = 256ull << 10;
-constexpr uint64_t kOpenFusedMinBytes = 1ull << 30;
-constexpr uint64_t kOpenFusedMaxBs = 2ull << 20;  // 256 lanes x 8 chunks
-
 // The composed route's scratch on stream s: `bytes`.
 static hipError_t open_get(hipStream_t s, size_t bytes, uint8_t **p) {
   SlotLock g(s);
@@ -940,17 +758,6 @@ static hipError_t open_get(hipStream_t s, size_t bytes, uint8_t **p) {
   hipError_t e = g.sl->open.ensure(s, bytes, kGrowFloor, 4, false);
   *p = g.sl->open.as<uint8_t>();
   return e;
-}
-
-template <int G>
-static hipError_t launch_open_g(const OArgs &a, bool aligned, hipStream_t s) {
-  const dim3 grid(uint32_t(a.n)), block(256);
-  if (aligned)
-    hipLaunchKernelGGL((k_open<G, true, 2>), grid, block, 0, s, a);
-  else
-    hipLaunchKernelGGL((k_open<G, false, 2>), grid, block, 0, s, a);
-  log_launch(kLaunchOpen, G, true, aligned, 2, 0, grid.x, a.n);
-  return hipGetLastError();
 }
 
 // Existing launches plus k_open_compare: the CID of the ctext and, when
@@ -964,27 +771,28 @@ static hipError_t launch_open_composed(const OpenJob &job, hipStream_t s) {
   hipError_t e = open_get(s, dig + (own_pt ? size_t(total) + 64 : 0), &scr);
   if (e != hipSuccess) return e;
   uint8_t *pt = own_pt ? scr + dig : job.ptext;
-  const uint64_t maxlen = job.n > 1 ? job.bs : job.last_len;
   PostJob pj{};
   pj.src = job.ctext;
   pj.stride = pj.msg_len = job.bs;
   pj.last_len = job.last_len;
   pj.n = job.n;
   pj.out = RefLayout{scr, ~0ull, 0};
-  KArgs a = make_args(pj);
-  for (int i = 0; i < 8; ++i) a.key[i] = job.cid_key[i];
-  a.base = job.cid_keyed ? kKeyed : 0u;
-  a.out_off = 0;
-  e = launch_pass<false>(a, maxlen, is_aligned(pj), s);
+  for (int i = 0; i < 8; ++i) pj.cid_key[i] = job.cid_key[i];
+  pj.cid_keyed = job.cid_keyed;
+  const Knobs k = knobs();
+  PostShape j = shape_of(pj);
+  const PassPlan p = plan_of(j, k);
+  e = launch_rec(dek_rec(j, p, 0, k), cid_args(pj), s);  // BLAKE3 only, the CID's key
   if (e != hipSuccess) return e;
   if (pt) {
-    e = launch_decrypt(job.ctext, pt, job.n, job.bs, job.last_len, job.refs, s);
+    e = decrypt_with(job.ctext, pt, job.n, job.bs, job.last_len, job.refs, k.latency_wgs, s);
     if (e != hipSuccess) return e;
   }
   if (job.salted) {
     pj.src = pt;
     for (int i = 0; i < 8; ++i) pj.salt[i] = job.salt[i];
-    e = launch_keyed_hash(pj, 32, s);
+    j.src_lo = low_bits(pt);
+    e = launch_rec(dek_rec(j, p, 32, k), dek_args(pj, 32), s);
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k_open_compare, dim3(uint32_t((job.n + 255) / 256)), dim3(256), 0, s,
@@ -996,11 +804,11 @@ hipError_t launch_open(const OpenJob &job, hipStream_t s) {
   if (job.n == 0) return hipSuccess;
   if (job.bs % 64 || job.bs > kMaxMsgLen || job.last_len > job.bs || job.n > 0x7fffffffull)
     return hipErrorInvalidValue;
-  const int route = g_open_route.load(std::memory_order_relaxed);
-  const bool able = job.salted && job.bs <= kOpenFusedMaxBs;
-  const bool wins = job.n >= kOpenFusedMinBlocks && job.bs >= kOpenFusedMinBs &&
-                    job.n * job.bs >= kOpenFusedMinBytes;
-  if (!able || route == 1 || (route == 0 && !wins)) return launch_open_composed(job, s);
+  const bool aligned = ((low_bits(job.ctext) | low_bits(job.ptext) | job.bs) & 15) == 0;
+  LaunchRec r;
+  if (!open_rec(job.n, job.bs, job.salted, aligned, g_open_route.load(std::memory_order_relaxed),
+                &r))
+    return launch_open_composed(job, s);
   OArgs a{};
   a.ctext = job.ctext;
   a.ptext = job.ptext;
@@ -1014,59 +822,37 @@ hipError_t launch_open(const OpenJob &job, hipStream_t s) {
     a.cid_key[i] = job.cid_key[i];
   }
   a.cid_base = job.cid_keyed ? kKeyed : 0u;
-  const bool aligned = ((reinterpret_cast<uintptr_t>(job.ctext) |
-                         reinterpret_cast<uintptr_t>(job.ptext) | uintptr_t(job.bs)) & 15) == 0;
-  const uint64_t C = (job.bs + 1023) >> 10;
-  const int g = C <= 256 ? 1 : C <= 512 ? 2 : C <= 1024 ? 4 : 8;
-  return with_g<1, 2, 4, 8>(g, [&](auto G) { return launch_open_g<G()>(a, aligned, s); });
+  // the one launch-and-log site of k_open
+  if (!launchable(r)) return hipErrorInvalidValue;
+  return with_g<kOpenGs>(r.g, [&](auto G) {
+    if (r.aligned)
+      hipLaunchKernelGGL((k_open<G(), true, 2>), dim3(r.grid), dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL((k_open<G(), false, 2>), dim3(r.grid), dim3(256), 0, s, a);
+    if (g_launch_log.on()) g_launch_log.append(r);
+    return hipGetLastError();
+  });
 }
 
 // ---- The ragged open (ragged_open_kernels.h) ----
-
-// The ragged open's buffers on stream s, in rag_get's form.
-static hipError_t rag_open_get(hipStream_t s, size_t plan, size_t cv, uint8_t **d_plan,
-                               uint8_t **d_cv, uint64_t **tot, uint64_t **d_tot) {
-  SlotLock g(s);
-  if (g.sd.e != hipSuccess) return g.sd.e;
-  hipError_t e = g.sl->otot.ensure();
-  if (e != hipSuccess) return e;
-  e = g.sl->oplan.ensure(s, plan, kGrowFloor, 4, false);
-  if (e != hipSuccess) return e;
-  e = g.sl->ocv.ensure(s, cv, kGrowFloor, 4, false);
-  if (e != hipSuccess) return e;
-  *d_plan = g.sl->oplan.as<uint8_t>();
-  *d_cv = g.sl->ocv.as<uint8_t>();
-  *tot = static_cast<uint64_t *>(g.sl->otot.h);
-  *d_tot = static_cast<uint64_t *>(g.sl->otot.d);
-  return hipSuccess;
-}
 
 // The chunk pass and the merge levels that have work, in mode MODE.
 template <int MODE>
 static hipError_t launch_rag_open_pass(ROArgs a, const uint64_t tot[3], hipStream_t s) {
   a.r.total = tot[0];
-  const uint64_t tiles = (tot[0] + 255) >> 8;
-  const dim3 grid(uint32_t(std::min<uint64_t>(tiles, 1u << 20))), block(256);
-  // few tiles: the compiler's ARX form, as launch_rag_chunk
-  if (tiles <= latency_wgs())
-    hipLaunchKernelGGL((k_rag_open_chunk<MODE, 0>), grid, block, 0, s, a);
+  const GridForm p = rag_chunk_plan(tot[0], knobs().latency_wgs);
+  if (p.form == 0)
+    hipLaunchKernelGGL((k_rag_open_chunk<MODE, 0>), dim3(p.grid), dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((k_rag_open_chunk<MODE, 2>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((k_rag_open_chunk<MODE, 2>), dim3(p.grid), dim3(256), 0, s, a);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (tot[1]) {
-    a.r.total = tot[1];
-    hipLaunchKernelGGL(k_rag_open_merge_a<MODE == 2>,
-                       dim3(uint32_t(std::min<uint64_t>(tot[1], 1u << 20))), dim3(256), 0, s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  if (tot[2]) {
-    a.r.total = tot[2];
-    hipLaunchKernelGGL(k_rag_open_merge_b<MODE == 2>,
-                       dim3(uint32_t(std::min<uint64_t>(tot[2], 1u << 20))), dim3(256), 0, s, a);
-    e = hipGetLastError();
-  }
+  auto merge = [&](auto k, uint64_t total) {  // a level that has work
+    a.r.total = total;
+    hipLaunchKernelGGL(k, dim3(capped_grid(total, 1u << 20)), dim3(256), 0, s, a);
+    return hipGetLastError();
+  };
+  if (e == hipSuccess && tot[1]) e = merge(k_rag_open_merge_a<MODE == 2>, tot[1]);
+  if (e == hipSuccess && tot[2]) e = merge(k_rag_open_merge_b<MODE == 2>, tot[2]);
   return e;
 }
 
@@ -1082,34 +868,12 @@ hipError_t launch_open_ragged(const OpenRaggedJob &job, hipStream_t s) {
   a.r.lo = kRaggedAll;
   a.r.hi = job.max_len;
   a.r.refs = const_cast<uint8_t *>(job.refs);
-  a.r.m = (job.n + kRagWG - 1) / kRagWG;
   a.status = job.status;
-  uint8_t *d_plan, *d_cv;
-  uint64_t *tot, *d_tot;
-  hipError_t e = rag_open_get(s, 8 * (job.n + 3 * (a.r.m + 1)), 0, &d_plan, &d_cv, &tot, &d_tot);
-  if (e != hipSuccess) return e;
-  a.r.pre = reinterpret_cast<uint64_t *>(d_plan);
-  a.r.wpre = a.r.pre + job.n;
   // a message above max_len is neither read nor written: it fails closed
-  hipLaunchKernelGGL(k_rag_count<true>, dim3(uint32_t(a.r.m)), dim3(kRagWG), 0, s, a.r,
-                     job.status, 1u /* GLFSX_BAD_CID */);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_rag_prefix<1024>, dim3(3), dim3(1024), 0, s, a.r.wpre, a.r.m, d_tot);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  // the one host wait of the call: the totals size the CV scratch and the
-  // launches below
-  e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return e;
-  const uint64_t totals[3] = {__atomic_load_n(tot + 0, __ATOMIC_RELAXED),
-                              __atomic_load_n(tot + 1, __ATOMIC_RELAXED),
-                              __atomic_load_n(tot + 2, __ATOMIC_RELAXED)};
-  if (totals[0] == 0) return hipSuccess;  // nothing selected
-  e = rag_open_get(s, 0, 64 * (totals[0] + totals[1]), &d_plan, &d_cv, &tot, &d_tot);
-  if (e != hipSuccess) return e;
-  a.r.cvs = reinterpret_cast<uint32_t *>(d_cv);
-  a.r.gcv = a.r.cvs + 16 * totals[0];
+  uint64_t totals[3];
+  hipError_t e = rag_plan<true>(a.r, &ScratchSlot::orag, 16, job.status, 1u /* GLFSX_BAD_CID */,
+                                totals, s);
+  if (e != hipSuccess || totals[0] == 0) return e;
   for (int i = 0; i < 8; ++i) {
     a.r.key[i] = job.cid_key[i];
     a.salt[i] = job.salt[i];

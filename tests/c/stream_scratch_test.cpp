@@ -320,6 +320,102 @@ static void test_pass_plan() {
   CHECK(quad_qpw(4 << 20) == 64 && quad_qpw((4 << 20) + 1) == 256);
 }
 
+// The families outside the log: values worked out by hand from the launch
+// code as it stood before the plans moved into launch_plan.h.
+static void test_other_plans() {
+  CHECK(arx_form(512, 512) == 0 && arx_form(513, 512) == 2 && arx_form(513, 512, 1) == 1);
+  {  // the ragged chunk passes: 256 chunks per tile, at most 2^20 workgroups
+    GridForm p = rag_chunk_plan(131072, 512);
+    CHECK(p.grid == 512 && p.form == 0);
+    p = rag_chunk_plan(131073, 512);
+    CHECK(p.grid == 513 && p.form == 2);
+    p = rag_chunk_plan((1ull << 28) + 1, 512);
+    CHECK(p.grid == (1u << 20) && p.form == 2);
+    p = rag_chunk_plan(1, 0);
+    CHECK(p.grid == 1 && p.form == 2);
+  }
+  {  // the small pass, either side of 256 * latency_wgs blobs
+    SmallPlan p = small_plan(131072, 4096, false, 512);
+    CHECK(p.g == 4 && !p.queue && p.form == 0 && p.wgs == 512 && p.n_coarse == 0);
+    p = small_plan(131072, 4096, true, 512);
+    CHECK(p.g == 4 && !p.queue && p.form == 0 && p.wgs == 512);
+    // G = 4: an eighth (16384) held back, 1792 coarse items, 16385 blobs in
+    // fine items of 16
+    p = small_plan(131073, 4096, false, 512);
+    CHECK(p.g == 4 && p.queue && p.form == 2 && p.n_coarse == 1792 && p.items == 2817 &&
+          p.wgs == 705);
+    p = small_plan(131073, 4096, true, 512);
+    CHECK(p.queue && p.form == 1 && p.n_coarse == 1792 && p.items == 2817 && p.wgs == 705);
+    // G = 1: nothing held back, the one blob left over is an item of its own
+    p = small_plan(131073, 1024, true, 512);
+    CHECK(p.g == 1 && p.queue && p.form == 1 && p.n_coarse == 2048 && p.items == 2049 &&
+          p.wgs == 513);
+    p = small_plan(131073, 1024, false, 131073);
+    CHECK(p.g == 1 && !p.queue && p.wgs == 513);
+    CHECK(small_plan(1, 0, false, 512).g == 1 && small_plan(1, 1025, false, 512).g == 2);
+    CHECK(small_plan(1, 2049, false, 512).g == 4 && small_plan(1, 16384, false, 512).g == 16);
+    CHECK(small_plan(1, 16385, false, 512).g == 0 && small_plan(1 << 20, 16385, true, 512).g == 0);
+    CHECK(capped_grid(705, 0) == 705 && capped_grid(705, 512) == 512);
+    CHECK(capped_grid(300, 512) == 300);
+  }
+  {  // launch_decrypt
+    // blocks of 65 keystream blocks: no 4 KiB units, 132 keystream blocks in all
+    DecryptPlan p = decrypt_plan(3, 4160, 100, true, 512);
+    CHECK(p.units == 0 && p.first_kb == 0 && p.grid == 1);
+    // 64 KiB blocks: 16 units each, a run per unit, nothing left for k_decrypt
+    p = decrypt_plan(4, 65536, 65536, true, 512);
+    CHECK(p.units == 64 && p.upb_shift == 4 && p.run_shift == 0 && p.lines.grid == 16 &&
+          p.lines.form == 0 && p.first_kb == 4096 && p.grid == 0);
+    CHECK(decrypt_plan(4, 65536, 65536, true, 16).lines.form == 0);
+    CHECK(decrypt_plan(4, 65536, 65536, true, 15).lines.form == 2);
+    // ... a short last block: 63 units, then 63 keystream blocks
+    p = decrypt_plan(4, 65536, 65536 - 100, true, 512);
+    CHECK(p.units == 63 && p.lines.grid == 16 && p.first_kb == 4032 && p.grid == 1);
+    // 1 MiB blocks, 2^20 units: runs of 16 leave exactly 65536 runs
+    p = decrypt_plan(4096, 1 << 20, 1 << 20, true, 512);
+    CHECK(p.units == (1u << 20) && p.upb_shift == 8 && p.run_shift == 4 &&
+          p.lines.grid == 16384 && p.lines.form == 2 && p.first_kb == (1u << 26) && p.grid == 0);
+    // ... a block fewer: runs of 16 would be 65520, so runs of 8
+    p = decrypt_plan(4095, 1 << 20, 1 << 20, true, 512);
+    CHECK(p.units == 1048320 && p.run_shift == 3 && p.lines.grid == 16384);
+    p = decrypt_plan(4097, 1 << 20, 1 << 20, true, 512);
+    CHECK(p.units == 1048832 && p.run_shift == 4 && p.lines.grid == 16384);
+    // three units per block: no shift, a run per unit
+    p = decrypt_plan(10, 12288, 12288, true, 512);
+    CHECK(p.units == 30 && p.upb_shift == 64 && p.run_shift == 0 && p.lines.grid == 8 &&
+          p.lines.form == 0 && p.first_kb == 1920 && p.grid == 0);
+    // unaligned buffers: k_decrypt alone, at most 65536 workgroups
+    p = decrypt_plan(2, 65536, 65536, false, 512);
+    CHECK(p.units == 0 && p.lines.grid == 0 && p.first_kb == 0 && p.grid == 8);
+    p = decrypt_plan(4096, 1 << 20, 1 << 20, false, 512);
+    CHECK(p.units == 0 && p.grid == 65536);
+  }
+  {  // a whole post at the defaults: the headline, config 2 and a latency-bound Create level
+    const Knobs k{2048, 512};
+    PostShape j{2048, 1 << 20, 1 << 20, 1 << 20, 0, 0, 0, true, ~0ull, 0, true};
+    PostRoute r = post_route(j, k);
+    CHECK(!r.fused && !r.cid.keystream && r.dek.family == kLaunchPass && r.dek.g == 4 &&
+          r.dek.form == 2 && r.cid.pass.g == 4 && r.cid.pass.chacha == 1 && r.cid.pass.form == 1 &&
+          r.cid.pass.grid == 2048);
+    j.n = 512;
+    j.msg_len = j.last_len = j.stride = 2 << 20;
+    r = post_route(j, k);  // 8 chunks per lane halved twice: 2048 workgroups, one launch
+    CHECK(r.fused && r.dek.family == kLaunchPassDc && r.dek.g == 2 && r.dek.split_log2 == 2 &&
+          r.dek.fine_div == 4 && r.dek.n == 512 && r.dek.grid == r.dek.items);
+    j.fuse = false;
+    r = post_route(j, k);
+    CHECK(!r.fused && r.dek.g == 2 && r.dek.split_log2 == 2 && r.dek.form == 2 &&
+          r.cid.pass.form == 2 && r.cid.pass.grid == 2048);
+    j.n = 1;  // one 2 MiB node: quad DEK pass, keystream + quad CID pass
+    r = post_route(j, k);
+    CHECK(!r.fused && r.dek.family == kLaunchQuad && r.dek.g == 64 && r.dek.split_log2 == 5 &&
+          r.cid.keystream && r.cid.ks_bs == (2u << 20) && r.cid.pass.family == kLaunchQuad);
+    j.has_ctext = false;  // no ctext in memory: the one k_pass launch
+    r = post_route(j, k);
+    CHECK(!r.cid.keystream && r.cid.pass.family == kLaunchPass && r.cid.pass.form == 0);
+  }
+}
+
 static LaunchRec rec(uint32_t tag) {
   return LaunchRec{kLaunchPass, tag, tag & 1, 1, 2, 0, tag + 1, 0, 0, tag + 2};
 }
@@ -396,6 +492,7 @@ int main() {
   test_registry();
   test_stream_device();
   test_pass_plan();
+  test_other_plans();
   if (g_failed) {
     fprintf(stderr, "stream_scratch_test: %d checks failed\n", g_failed);
     return 1;

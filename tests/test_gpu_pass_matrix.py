@@ -1,6 +1,6 @@
 """One row per reachable instantiation of the bulk-pass kernels.
 
-The host code in glfs_amd/csrc/post_kernels.hip picks a kernel from the shape,
+The host code (glfs_amd/csrc/launch_plan.h) picks a kernel from the shape,
 the pointer alignment and two tuning values.  Every row below names the
 smallest shape and knob setting that selects one instantiation, and the
 launch log (glfsx_debug_pass_log) says which kernel the call really ran: a
@@ -8,10 +8,11 @@ case resets the log, makes one call, asserts that the records equal the
 row's expectation and only then compares bytes with the oracle, bit for bit.
 A shape that stops reaching its kernel after a retuning fails here.
 
-test_table_covers_the_reachable_set builds the set of instantiations the
-dispatch can reach from the constants in the sources (the with_g lists, the
-form-1 rule of launch_g, quad_qpw, the G lists of k_pass_dc and k_open) and
-asserts that the rows' expectations cover exactly that set.  It needs no GPU.
+test_table_covers_the_reachable_set asks the selection itself
+(glfs_amd/csrc/launch_plan.h, pure functions) which instantiations it can
+return: a stand-alone program (tests/c/launch_plan_sweep.cpp) sweeps it over
+shapes and knob values, and the rows' expectations must cover exactly that
+set, which is also the set the dispatchers can launch.  It needs no GPU.
 
 Knobs: set_split_target(0) fixes G from the block size (no split up to
 16 MiB blocks); set_latency_wgs(0) gives ARX forms 1/2, set_latency_wgs(1 <<
@@ -37,7 +38,8 @@ import ctypes
 import functools
 import os
 import random
-import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -77,7 +79,7 @@ def dek_blocks_c(g):
 
 
 def cid_form(g):
-    """launch_g: the aligned CID pass without split runs form 1 from G = 4."""
+    """pass_rec: the aligned CID pass without split runs form 1 from G = 4."""
     return 1 if g >= 4 else 2
 
 
@@ -214,59 +216,60 @@ def table_kernels():
 
 
 # ------------------------------------------------------------- the meta-test
-def _with_g(src, callee):
-    """The G list of the with_g<...> call whose body names `callee`."""
-    hits = [m for m in re.finditer(r"with_g<([\d,\s]+)>\(\s*\w+,\s*\[&\]\(auto G\)\s*\{(.*?)\}\s*\)",
-                                   src, re.S) if callee in m.group(2)]
-    assert len(hits) == 1, (callee, len(hits))
-    return tuple(int(x) for x in hits[0].group(1).split(","))
+def _sweep_program(tmp_path):
+    """tests/c/launch_plan_sweep.cpp, built with the host compiler under
+    AddressSanitizer and UBSan (as tests/test_host_units.py builds its
+    programs): its own main, nothing loaded into Python."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.fail("no host C++ compiler")
+    out = str(tmp_path / "launch_plan_sweep")
+    subprocess.check_call(
+        [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
+         "-fno-sanitize-recover=undefined", "-I", CSRC,
+         os.path.join(ROOT, "tests", "c", "launch_plan_sweep.cpp"), "-o", out])
+    return out
 
 
-def reachable_kernels():
-    src = open(os.path.join(CSRC, "post_kernels.hip")).read()
-    plan = open(os.path.join(CSRC, "launch_plan.h")).read()
-    pass_gs = _with_g(src, "launch_g<G(), CHACHA>")
-    dc_gs = _with_g(src, "k_pass_dc<G()>")
-    open_gs = _with_g(src, "launch_open_g<G()>")
-    # launch_g: form 0 when aligned and latency-bound; otherwise form 1 for
-    # the aligned CID pass with G >= 4 and no split, form 2 for the rest
-    m = re.search(r"if constexpr \(CHACHA\) \{\s*if \(G >= (\d+) && a\.split_log2 == 0\) \{\s*"
-                  r"hipLaunchKernelGGL\(\(k_pass<G, true, true, 1>\)", src)
-    assert m, "launch_g's form-1 rule has changed: update this test with it"
-    form1_from = int(m.group(1))
-    for form, args in ((0, "G, CHACHA, true, 0"), (2, "G, CHACHA, true, 2"),
-                       (2, "G, CHACHA, false, 2")):
-        assert src.count("(k_pass<%s>)" % args) == 1, args
-    m = re.search(r"inline int quad_qpw\(uint64_t maxlen\) \{ return maxlen <= .*? \? (\d+) : (\d+); \}",
-                  plan)
-    assert m, "quad_qpw has changed: update this test with it"
-    qpws = (int(m.group(1)), int(m.group(2)))
-    for q in qpws:
-        assert "k_quad<%d>" % q in src
-    ks = set()
-    for g in pass_gs:
-        for chacha in (0, 1):
-            ks.add((PASS, g, chacha, 1, 0))
-            ks.add((PASS, g, chacha, 0, 2))
-            # aligned form 2: every DEK pass; the CID pass below form1_from,
-            # and from there on with a split (pass_plan halves any G > 1,
-            # and the largest G splits by size)
-            ks.add((PASS, g, chacha, 1, 2))
-        if g >= form1_from:
-            ks.add((PASS, g, 1, 1, 1))
-    ks |= {(QUAD, q, 0, 1, 0) for q in qpws}
-    ks |= {(PASS_DC, g, 1, 1, 2) for g in dc_gs}
-    ks |= {(OPEN, g, 1, a, 2) for g in open_gs for a in (0, 1)}
-    return ks
+def _run(cmd):
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert "launch_plan_sweep: ok" in p.stdout
+    assert p.stderr == "", p.stderr  # the sanitizers report nothing
+    return p.stdout
 
 
-def test_table_covers_the_reachable_set():
-    want, have = reachable_kernels(), table_kernels()
+@pytest.fixture(scope="module")
+def sweep_program(tmp_path_factory):
+    return _sweep_program(tmp_path_factory.mktemp("sweep"))
+
+
+def reachable_kernels(program):
+    """What launch_plan.h's pure functions return over a sweep of shapes,
+    alignments and knob values.  The program itself fails unless that set is
+    the constexpr launchable set the dispatchers instantiate."""
+    return {tuple(int(x) for x in ln.split()[1:]) for ln in _run([program]).splitlines()
+            if ln.startswith("K ")}
+
+
+def test_table_covers_the_reachable_set(sweep_program):
+    want, have = reachable_kernels(sweep_program), table_kernels()
     assert have == want, (sorted(want - have), sorted(have - want))
+    assert len(want) == 60
     assert len({(r.g, r.name) for r in PASS_ROWS}) == len(PASS_ROWS)
     # every k_pass row belongs to one parametrised group
     assert all(sum(r.name.startswith(p + "-") or r.name == p for p in PASS_GROUPS) == 1
                for r in PASS_ROWS)
+
+
+def test_selection_matches_the_recorded_launches(sweep_program):
+    """tests/golden/launch_records.txt: what the library launched for a fixed
+    list of calls (scripts/record_launches.py) before the selection moved
+    into launch_plan.h.  The pure functions give exactly those records."""
+    fixture = os.path.join(ROOT, "tests", "golden", "launch_records.txt")
+    n = sum(1 for _ in open(fixture))
+    assert n >= 200
+    assert "replayed %d\n" % n in _run([sweep_program, fixture])
 
 
 def test_log_hook_needs_no_device():
