@@ -26,6 +26,9 @@ GLFSX_E_IO = -8
 GLFSX_E_CORRUPT = -9
 GLFSX_BAD_CID = 1
 GLFSX_BAD_DEK = 2
+GLFSX_TREE_NONCANON = 1
+GLFSX_TREE_ORDER = 2
+GLFSX_TREE_NAME = 4
 GLFSX_STORE_TRUST = 0
 GLFSX_STORE_HASH = 1
 
@@ -138,6 +141,11 @@ SIGNATURES = {
                                  ctypes.POINTER(ctypes.c_uint64), _VP]),
     "glfsx_tree_encode_device": (_INT, [_U64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                         _U64, _VP, ctypes.POINTER(ctypes.c_uint64), _VP]),
+    "glfsx_tree_decode": (_INT, [_VP, _U64, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _VP,
+                                 _VP, _U64, ctypes.POINTER(ctypes.c_uint64)]),
+    "glfsx_tree_decode_device": (_INT, [_VP, _U64, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _VP,
+                                        _VP, _VP, _VP, _U64, ctypes.POINTER(ctypes.c_uint64),
+                                        _VP]),
     "glfsx_fill_splitmix_blobs_device": (_INT, [_VP, _U64, _U64, _U64, _VP]),
     "glfsx_post_tree_device": (_INT, [_U64, _U64, _CP, _CP, _CP, _VP, _VP, _VP, _U64, _VP,
                                       _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U64, _VP, _U64,

@@ -550,3 +550,74 @@ int glfsx_tree_encode_device(uint64_t n, const uint8_t *d_names,
   return 0;
 }
 
+int glfsx_tree_decode_device(const void *d_data, uint64_t len, uint8_t *d_names,
+                             uint64_t names_cap, uint64_t *d_name_offs, uint32_t *d_modes,
+                             uint8_t *d_types, uint64_t types_cap, uint64_t *d_type_offs,
+                             uint8_t *d_roots, uint64_t *d_sizes, uint64_t *d_block_sizes,
+                             uint32_t *d_status, uint64_t n_cap, uint64_t counts[5],
+                             void *stream) {
+  Ctx *c;
+  if (int e = ctx_get(&c)) return e;  // before any argument is looked at
+  if (!counts || (len && !d_data)) return fail(GLFSX_E_ARG, "null argument");
+  for (int k = 0; k < 5; ++k) counts[k] = 0;
+  if (len > (1ull << 40)) return fail(GLFSX_E_UNSUPPORTED, "tree bytes above 2^40");
+  hipStream_t s = pick_stream(c, stream);
+  if (len == 0) {  // no lines: the two offset arrays hold their one word
+    if (d_name_offs) HIP_TRY(hipMemsetAsync(d_name_offs, 0, 8, s));
+    if (d_type_offs) HIP_TRY(hipMemsetAsync(d_type_offs, 0, 8, s));
+    HIP_TRY(stream_wait(s));
+    return 0;
+  }
+  // every line has a byte, so len bounds n; at least one word of index
+  const uint64_t cap = std::max<uint64_t>(1, std::min(n_cap, len));
+  if (tree_decode_wgs(cap) > 0x7FFFFFFFull)
+    return fail(GLFSX_E_UNSUPPORTED, "n_cap above the kernels' grid limit");
+  TreeDecodeJob j{};
+  j.data = static_cast<const uint8_t *>(d_data);
+  j.len = len;
+  j.n_cap = cap;
+  if (int e = c->d_tree.ensure(8 * tree_decode_words(j.data, len, cap))) return e;
+  if (int e = c->h_small.ensure(64)) return e;
+  j.scratch = reinterpret_cast<uint64_t *>(c->d_tree.p);
+  j.names = d_names;
+  j.names_cap = names_cap;
+  j.name_offs = d_name_offs;
+  j.modes = d_modes;
+  j.types = d_types;
+  j.types_cap = types_cap;
+  j.type_offs = d_type_offs;
+  j.roots = d_roots;
+  j.sizes = d_sizes;
+  j.block_sizes = d_block_sizes;
+  j.status = d_status;
+  if (n_cap == 0) {  // no room for a line: counts only (the index still has a word)
+    j.names = j.types = j.roots = nullptr;
+    j.name_offs = j.type_offs = j.sizes = j.block_sizes = nullptr;
+    j.modes = j.status = nullptr;
+  }
+  HIP_TRY(launch_tree_decode(j, s));
+  HIP_TRY(hipMemcpyAsync(c->h_small.p, j.scratch, 40, hipMemcpyDeviceToHost, s));
+  HIP_TRY(stream_wait(s));
+  memcpy(counts, c->h_small.p, 40);
+  const bool per_line = d_name_offs || d_modes || d_type_offs || d_roots || d_sizes ||
+                        d_block_sizes || d_status;
+  if (counts[0] > cap) {  // the index could not hold the lines: nothing was parsed
+    counts[1] = counts[2] = counts[3] = 0;
+    return fail(GLFSX_E_ARG, "%llu tree lines, n_cap holds %llu", (unsigned long long)counts[0],
+                (unsigned long long)cap);
+  }
+  if (per_line && counts[0] > n_cap)
+    return fail(GLFSX_E_ARG, "%llu tree lines, n_cap holds %llu", (unsigned long long)counts[0],
+                (unsigned long long)n_cap);
+  if ((d_names && counts[1] > names_cap) || (d_types && counts[2] > types_cap))
+    return fail(GLFSX_E_ARG, "decoded names / types need %llu / %llu bytes, buffers hold %llu / %llu",
+                (unsigned long long)counts[1], (unsigned long long)counts[2],
+                (unsigned long long)names_cap, (unsigned long long)types_cap);
+  if (n_cap == 0) {  // a tail alone: the offset arrays' one word
+    if (d_name_offs) HIP_TRY(hipMemsetAsync(d_name_offs, 0, 8, s));
+    if (d_type_offs) HIP_TRY(hipMemsetAsync(d_type_offs, 0, 8, s));
+    HIP_TRY(stream_wait(s));
+  }
+  return 0;
+}
+

@@ -312,6 +312,38 @@ hipError_t launch_tree_layout(const TreeJob &j, hipStream_t s);
 // small enough to run beside the small-blob DEK pass.
 hipError_t launch_tree_static(const TreeJob &j, hipStream_t s);
 
+// The inverse (tree_decode_kernels.h): see glfsx_tree_decode_device.  Seven
+// launches whatever n or len.  len > 0, n_cap > 0.
+constexpr uint32_t kTdSpan = 16 * 1024;  // bytes per workgroup of the count / index passes
+struct TreeDecodeJob {
+  const uint8_t *data;
+  uint64_t len;
+  uint64_t n_cap;     // lines the index and every per-line output hold
+  // tree_decode_words(data, len, n_cap) words.  The first five are the
+  // results once the launches have completed: n, bytes of names, bytes of
+  // types, n_bad (a tail counted), tail
+  uint64_t *scratch;
+  uint8_t *names;     // every output nullable
+  uint64_t names_cap;
+  uint64_t *name_offs;
+  uint32_t *modes;
+  uint8_t *types;
+  uint64_t types_cap;
+  uint64_t *type_offs;
+  uint8_t *roots;
+  uint64_t *sizes, *block_sizes;
+  uint32_t *status;
+};
+// spans are cut from the 16-byte boundary at or below data
+inline uint64_t tree_decode_spans(const uint8_t *data, uint64_t len) {
+  return ((reinterpret_cast<uintptr_t>(data) & 15) + len + kTdSpan - 1) / kTdSpan;
+}
+inline uint64_t tree_decode_wgs(uint64_t n_cap) { return (n_cap + kTreeWG - 1) / kTreeWG; }
+inline uint64_t tree_decode_words(const uint8_t *data, uint64_t len, uint64_t n_cap) {
+  return 8 + tree_decode_spans(data, len) + 2 * tree_decode_wgs(n_cap) + 3 * n_cap;
+}
+hipError_t launch_tree_decode(const TreeDecodeJob &j, hipStream_t s);
+
 // n blobs of len bytes (len % 8 == 0), blob b = the splitmix stream of seed
 // seed0 + b (see oracle_fill_splitmix_blobs).
 hipError_t launch_fill_blobs(uint8_t *dst, uint64_t n, uint64_t len, uint64_t seed0,

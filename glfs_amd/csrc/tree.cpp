@@ -1,4 +1,6 @@
-// tree.cpp -- host encoder of glfs tree blobs (tree.go:284-320 TreeWriter).
+// tree.cpp -- host encoder of glfs tree blobs (tree.go:284-320 TreeWriter)
+// and its inverse, the decoder of canonical lines (glfsx_tree_decode; the
+// grammar is tree_line.h's, shared with the kernels).
 //
 // A tree blob is JSON lines, one TreeEntry per Put (tree.go:300-316), written
 // by Go's json.Encoder: struct fields in declaration order with their tags
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "../../include/glfsx.h"
+#include "tree_line.h"
 
 namespace {
 
@@ -214,6 +217,139 @@ extern "C" int glfsx_tree_encode(uint64_t n, const uint8_t *names,
   if (out_cap < acc) return GLFSX_E_ARG;
   parallel_ranges(n, [&](uint64_t, uint64_t a, uint64_t b) {
     for (uint64_t i = a; i < b; ++i) line(e, i, out + (i ? L[i - 1] : 0));
+  });
+  return GLFSX_OK;
+}
+
+// ---------------------------------------------------------------- decoder
+namespace {
+
+struct Rec {  // one line after the parse pass
+  glfsx::TlLine L;
+  uint32_t status;
+};
+
+}  // namespace
+
+extern "C" int glfsx_tree_decode(const uint8_t *data, uint64_t len, uint8_t *names,
+                                 uint64_t names_cap, uint64_t *name_offs, uint32_t *modes,
+                                 uint8_t *types, uint64_t types_cap, uint64_t *type_offs,
+                                 uint8_t *roots, uint64_t *sizes, uint64_t *block_sizes,
+                                 uint32_t *status, uint64_t n_cap, uint64_t counts[5]) {
+  using namespace glfsx;
+  if (!counts || (len && !data)) return GLFSX_E_ARG;
+  for (int k = 0; k < 5; ++k) counts[k] = 0;
+  // pass 1: where the lines end (every 0x0A ends one), by byte ranges
+  unsigned hw = std::thread::hardware_concurrency();
+  const uint64_t nt = std::min<uint64_t>(std::min(16u, hw ? hw : 1u),
+                                         std::max<uint64_t>(1, len >> 20));
+  std::vector<uint64_t> cnt(nt + 1, 0);
+  auto bytes_pass = [&](auto f) {
+    if (nt <= 1) return f(0, 0, len);
+    std::vector<std::thread> th;
+    for (uint64_t k = 0; k < nt; ++k) th.emplace_back(f, k, len * k / nt, len * (k + 1) / nt);
+    for (auto &x : th) x.join();
+  };
+  bytes_pass([&](uint64_t k, uint64_t a, uint64_t b) {
+    uint64_t c = 0;
+    for (const uint8_t *q = data + a, *e = data + b;
+         q < e && (q = static_cast<const uint8_t *>(memchr(q, '\n', size_t(e - q)))); ++q)
+      ++c;
+    cnt[k + 1] = c;
+  });
+  for (uint64_t k = 0; k < nt; ++k) cnt[k + 1] += cnt[k];
+  const uint64_t n = cnt[nt];
+  const bool tail = len && data[len - 1] != '\n';
+  std::vector<uint64_t> ends(n);  // index of each line's '\n'
+  bytes_pass([&](uint64_t k, uint64_t a, uint64_t b) {
+    uint64_t c = cnt[k];
+    for (const uint8_t *q = data + a, *e = data + b;
+         q < e && (q = static_cast<const uint8_t *>(memchr(q, '\n', size_t(e - q)))); ++q)
+      ends[c++] = uint64_t(q - data);
+  });
+  // pass 2: the grammar, and the decoded lengths
+  std::vector<Rec> rec(n);
+  parallel_ranges(n, [&](uint64_t, uint64_t a, uint64_t b) {
+    for (uint64_t i = a; i < b; ++i) {
+      Rec &r = rec[i];
+      r.L = TlLine{};
+      r.status = tl_parse(data, i ? ends[i - 1] + 1 : 0, ends[i], &r.L) ? 0 : GLFSX_TREE_NONCANON;
+      if (r.status) r.L = TlLine{};  // its columns are zero / empty
+    }
+  });
+  // pass 3: name rule and order (the decoded name against the line before)
+  parallel_ranges(n, [&](uint64_t, uint64_t a, uint64_t b) {
+    for (uint64_t i = a; i < b; ++i) {
+      if (rec[i].status & GLFSX_TREE_NONCANON) continue;
+      const bool prev = i && !(rec[i - 1].status & GLFSX_TREE_NONCANON);
+      rec[i].status |= tl_name_bits(data, rec[i].L.name_at, data,
+                                    prev ? rec[i - 1].L.name_at : 0, prev, nullptr);
+    }
+  });
+  uint64_t nl = 0, tl = 0, bad = tail;
+  for (uint64_t i = 0; i < n; ++i) {
+    nl += rec[i].L.name_len;
+    tl += rec[i].L.type_len;
+    bad += rec[i].status != 0;
+  }
+  counts[0] = n;
+  counts[1] = nl;
+  counts[2] = tl;
+  counts[3] = bad;
+  counts[4] = tail;
+  const bool per_line = name_offs || modes || type_offs || roots || sizes || block_sizes || status;
+  if ((per_line && n > n_cap) || (names && nl > names_cap) || (types && tl > types_cap))
+    return GLFSX_E_ARG;  // nothing written; the counts say what is needed
+  // pass 4: the columns.  Offsets first (serial), then every thread its lines.
+  if (name_offs || type_offs || names || types) {
+    std::vector<uint64_t> no(names ? n : 0), to(types ? n : 0);
+    uint64_t a = 0, b = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+      if (name_offs) name_offs[i] = a;
+      if (type_offs) type_offs[i] = b;
+      if (names) no[i] = a;
+      if (types) to[i] = b;
+      a += rec[i].L.name_len;
+      b += rec[i].L.type_len;
+    }
+    if (name_offs) name_offs[n] = a;
+    if (type_offs) type_offs[n] = b;
+    parallel_ranges(n, [&](uint64_t, uint64_t x, uint64_t y) {
+      for (uint64_t i = x; i < y; ++i) {
+        if (rec[i].status & GLFSX_TREE_NONCANON) continue;
+        if (names) {
+          TlUnescape<const uint8_t *> u(data, rec[i].L.name_at);
+          uint8_t *o = names + no[i];
+          for (int c; (c = u.next()) >= 0;) *o++ = uint8_t(c);
+        }
+        if (types) {
+          TlUnescape<const uint8_t *> u(data, rec[i].L.type_at);
+          uint8_t *o = types + to[i];
+          for (int c; (c = u.next()) >= 0;) *o++ = uint8_t(c);
+        }
+      }
+    });
+  }
+  parallel_ranges(n, [&](uint64_t, uint64_t x, uint64_t y) {
+    for (uint64_t i = x; i < y; ++i) {
+      const Rec &r = rec[i];
+      if (modes) modes[i] = r.L.mode;
+      if (sizes) sizes[i] = r.L.size;
+      if (block_sizes) block_sizes[i] = r.L.block_size;
+      if (status) status[i] = r.status;
+      if (!roots) continue;
+      if (r.status & GLFSX_TREE_NONCANON) {
+        memset(roots + 64 * i, 0, 64);
+        continue;
+      }
+      for (int h = 0; h < 2; ++h) {
+        uint32_t w[16], o[8];
+        tl_load_words(data, r.L.cid_at + h * kTlDekAfterCid, w, 16);
+        tl_unhex64(w, o);
+        for (int k = 0; k < 8; ++k)
+          for (int q = 0; q < 4; ++q) roots[64 * i + 32 * h + 4 * k + q] = uint8_t(o[k] >> (8 * q));
+      }
+    }
   });
   return GLFSX_OK;
 }

@@ -19,11 +19,14 @@
 // ds_write_b128) and stores them with aligned 16-byte stores (bytes at the two partial 16-byte granules of a
 // workgroup's span, which it shares with its neighbours, are stored one by
 // one).  A workgroup whose lines do not fit the LDS image stores bytes.
+//
+// The read side of the same bytes is tree_decode_kernels.h, included below.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device_common.h"
 #include "kernels.h"
+#include "tree_line.h"
 
 namespace glfsx {
 namespace {
@@ -528,5 +531,9 @@ hipError_t launch_fill_blobs(uint8_t *dst, uint64_t n, uint64_t len, uint64_t se
                      reinterpret_cast<uint64_t *>(dst), n, len / 8, seed0);
   return hipGetLastError();
 }
+
+// the decoder of the same lines: k_td_count / k_td_index / k_td_parse /
+// k_td_write and launch_tree_decode
+#include "tree_decode_kernels.h"
 
 }  // namespace glfsx

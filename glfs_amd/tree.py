@@ -347,9 +347,140 @@ def post_tree_map(machine: "glfs.Machine", store, m: dict,
 
 
 # ------------------------------------------------------------------ reader
+@dataclass
+class TreeColumns:
+    """What glfsx_tree_decode[_device] gives: the columns encode_lines takes
+    entries apart into.  Host form: numpy arrays (names / types uint8,
+    name_offs / type_offs / sizes / block_sizes uint64, modes / status uint32,
+    roots uint8 of 64 n: CID || DEK); device form: torch tensors on the GPU
+    (the 64-bit columns as int64, modes / status as int32).  status[i]: a set
+    of _native.GLFSX_TREE_NONCANON / _ORDER / _NAME; n_bad counts the lines
+    with a non-zero status, plus one for a tail (bytes after the last
+    newline)."""
+    n: int
+    names: object
+    name_offs: object
+    modes: object
+    types: object
+    type_offs: object
+    roots: object
+    sizes: object
+    block_sizes: object
+    status: object
+    n_bad: int
+    tail: bool
+
+
+def decode_lines(data) -> TreeColumns:
+    """The inverse of encode_lines, natively on host cores
+    (glfsx_tree_decode): canonical lines -- byte for byte what the encoder
+    writes -- are decoded, every other line is reported in status."""
+    import ctypes
+    import numpy as np
+    from . import _native as N
+    buf = np.frombuffer(data, dtype=np.uint8)
+    ln = buf.size
+    ptr = buf.ctypes.data if ln else None
+    counts = (ctypes.c_uint64 * 5)()
+    N.check(N.lib.glfsx_tree_decode(ptr, ln, None, 0, None, None, None, 0, None, None, None,
+                                    None, None, 0, counts))
+    n, nl, tl = counts[0], counts[1], counts[2]
+    c = TreeColumns(n, np.empty(nl, np.uint8), np.empty(n + 1, np.uint64),
+                    np.empty(n, np.uint32), np.empty(tl, np.uint8), np.empty(n + 1, np.uint64),
+                    np.empty(64 * n, np.uint8), np.empty(n, np.uint64), np.empty(n, np.uint64),
+                    np.empty(n, np.uint32), 0, False)
+    N.check(N.lib.glfsx_tree_decode(ptr, ln, c.names.ctypes.data, nl, c.name_offs.ctypes.data,
+                                    c.modes.ctypes.data, c.types.ctypes.data, tl,
+                                    c.type_offs.ctypes.data, c.roots.ctypes.data,
+                                    c.sizes.ctypes.data, c.block_sizes.ctypes.data,
+                                    c.status.ctypes.data, n, counts))
+    c.n_bad, c.tail = counts[3], bool(counts[4])
+    return c
+
+
+# the shortest canonical line: empty name and type, one-digit numbers
+_MIN_LINE = len('{"name":"","mode":0,"ref":{"type":"","cid":"","dek":"","size":0,"blockSize":0}}\n') + 128
+
+
+def decode_lines_device(d_data: int, length: int, stream=None) -> TreeColumns:
+    """decode_lines over `length` bytes of device memory at d_data, on the
+    GPU (glfsx_tree_decode_device): the columns as torch tensors on the
+    current device."""
+    import ctypes
+    import torch
+    from . import _native as N
+    counts = (ctypes.c_uint64 * 5)()
+    nul = [None, 0, None, None, None, 0, None, None, None, None, None]
+    n_cap = length // _MIN_LINE + 1  # holds every all-canonical input
+    rc = N.lib.glfsx_tree_decode_device(d_data, length, *nul, n_cap, counts, stream)
+    if rc == N.GLFSX_E_ARG and counts[0] > n_cap:  # non-canonical lines, shorter ones
+        n_cap = counts[0]
+        rc = N.lib.glfsx_tree_decode_device(d_data, length, *nul, n_cap, counts, stream)
+    N.check(rc)
+    n, nl, tl = counts[0], counts[1], counts[2]
+    e = lambda k, dt: torch.empty(k, dtype=dt, device="cuda")
+    c = TreeColumns(n, e(nl, torch.uint8), e(n + 1, torch.int64), e(n, torch.int32),
+                    e(tl, torch.uint8), e(n + 1, torch.int64), e(64 * n, torch.uint8),
+                    e(n, torch.int64), e(n, torch.int64), e(n, torch.int32), 0, False)
+    N.check(N.lib.glfsx_tree_decode_device(
+        d_data, length, c.names.data_ptr(), nl, c.name_offs.data_ptr(), c.modes.data_ptr(),
+        c.types.data_ptr(), tl, c.type_offs.data_ptr(), c.roots.data_ptr(), c.sizes.data_ptr(),
+        c.block_sizes.data_ptr(), c.status.data_ptr(), n, counts, stream))
+    c.n_bad, c.tail = counts[3], bool(counts[4])
+    return c
+
+
+def entries_from_columns(c: TreeColumns) -> list:
+    """The TreeEntry list of host columns whose every status is 0 (so every
+    name is valid UTF-8, in order and clean)."""
+    names, types, roots = c.names.tobytes(), c.types.tobytes(), c.roots.tobytes()
+    no, to = c.name_offs.tolist(), c.type_offs.tolist()
+    modes, sizes, bss = c.modes.tolist(), c.sizes.tolist(), c.block_sizes.tolist()
+    tcache: dict = {}
+    out = []
+    # Four small objects an entry and none can be part of a cycle: with the
+    # cyclic collector left on, its passes over the growing list take three
+    # quarters of the time at 2^20 entries.
+    import gc
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        for i in range(c.n):
+            tb = types[to[i]:to[i + 1]]
+            ty = tcache.get(tb)
+            if ty is None:
+                ty = tcache[tb] = tb.decode("utf-8")
+            r = 64 * i
+            out.append(TreeEntry(names[no[i]:no[i + 1]].decode("utf-8"), modes[i],
+                                 glfs.Ref(ty, Root(bigblob.Ref(roots[r:r + 32],
+                                                               roots[r + 32:r + 64]),
+                                                   sizes[i], bss[i]))))
+    finally:
+        if was_on:
+            gc.enable()
+    return out
+
+
 def read_tree_bytes(data: bytes, cid_from_json=_cid_from_json) -> list:
     """TreeReader.Next over the decoded bytes (tree.go:340-372): a stream of
-    JSON values, each a TreeEntry, strictly increasing names, each valid."""
+    JSON values, each a TreeEntry, strictly increasing names, each valid.
+
+    With the default cid form the bytes go through the native decoder
+    (decode_lines).  If it vouches for every line -- all canonical, in order,
+    names clean, no tail -- the entries are built from its columns; on any
+    other outcome read_tree_bytes_py decodes the bytes as before, with its
+    results and error texts."""
+    if cid_from_json is _cid_from_json:
+        c = decode_lines(data)
+        if c.n_bad == 0:
+            return entries_from_columns(c)
+    return read_tree_bytes_py(data, cid_from_json)
+
+
+def read_tree_bytes_py(data: bytes, cid_from_json=_cid_from_json) -> list:
+    """read_tree_bytes with Python's JSON decoder, one raw_decode per entry:
+    any JSON the reference reads, any cid form; the yardstick of the native
+    path."""
     dec = json.JSONDecoder()
     s = data.decode("utf-8", "replace")
     i, n, out, last = 0, len(s), [], ""

@@ -35,6 +35,8 @@
  *                          block from host memory: one launch up to 64 KiB
  *   glfsx_depth            bigblob/blob.go:256-264 depth()
  *   glfsx_tree_encode      tree.go:300-316 TreeWriter.Put's JSON lines, batched
+ *   glfsx_tree_decode      tree.go:340-372 TreeReader.Next's decoding of those
+ *                          lines, batched; canonical lines only, others reported
  *   glfsx_store_*          the store under ref.go:103 (bcsdk.WO / MemStore [ext])
  *                          with a pre-hashed Post that takes the GPU CID
  *   glfsx_chacha20_xor*    bigblob/ref.go:137-144  cryptoXOR (read side decrypt)
@@ -445,6 +447,49 @@ int glfsx_tree_encode_device(uint64_t n, const uint8_t *d_names,
                              const uint64_t *d_block_sizes, void *d_out,
                              uint64_t out_cap, uint64_t *d_line_ends,
                              uint64_t *out_len, void *stream);
+
+/* The inverse: the lines of a tree blob (data, len bytes, untrusted) back to
+ * the encoder's inputs, on host cores.  It decodes canonical lines only -- a
+ * line that is byte for byte one glfsx_tree_encode can write, '\n' included
+ * (the grammar is glfs_amd/csrc/tree_line.h) -- and reports every other line
+ * for a general JSON decoder.  Every 0x0A ends a line; bytes after the last
+ * one are a tail.  status[i] is a set of:
+ *   GLFSX_TREE_NONCANON: line i is not canonical; its strings are empty and
+ *     its other columns zero;
+ *   GLFSX_TREE_ORDER: its decoded name is byte-wise <= the line's before it
+ *     (tree.go:371); only when both lines are canonical;
+ *   GLFSX_TREE_NAME: its name fails TreeEntry.Validate (tree.go:80-89).
+ * counts[0] = n lines, [1] = bytes of all names, [2] = of all types, [3] =
+ * n_bad (lines with a non-zero status, plus one for a tail), [4] = 1 if
+ * there is a tail: always set.  Every output is nullable (all NULL: the
+ * counts only).  name_offs / type_offs hold n + 1 words, roots 64 n bytes;
+ * n_cap is the capacity in lines of every per-line output, names_cap /
+ * types_cap the bytes at names / types: if one is too small the call returns
+ * GLFSX_E_ARG with nothing written and the counts set. */
+#define GLFSX_TREE_NONCANON 1u
+#define GLFSX_TREE_ORDER 2u
+#define GLFSX_TREE_NAME 4u
+int glfsx_tree_decode(const uint8_t *data, uint64_t len, uint8_t *names,
+                      uint64_t names_cap, uint64_t *name_offs, uint32_t *modes,
+                      uint8_t *types, uint64_t types_cap, uint64_t *type_offs,
+                      uint8_t *roots, uint64_t *sizes, uint64_t *block_sizes,
+                      uint32_t *status, uint64_t n_cap, uint64_t counts[5]);
+
+/* The same on the GPU: d_data and every output in device memory, counts on
+ * the host.  Seven launches whatever n or len (count the line ends, scan,
+ * index them, parse, scan the name and the type lengths, write), enqueued on
+ * `stream`, which is synchronised once to return the counts.  The line index
+ * lives in the library's scratch, n_cap words of it, so n_cap bounds the
+ * lines even when every output is NULL: with n above n_cap the call returns
+ * GLFSX_E_ARG with counts[0] = n and counts[4] set and the other counts 0.
+ * Otherwise as glfsx_tree_decode, a too-small capacity included (nothing is
+ * written).  len is at most 2^40.  Without a device: GLFSX_E_DEVICE. */
+int glfsx_tree_decode_device(const void *d_data, uint64_t len, uint8_t *d_names,
+                             uint64_t names_cap, uint64_t *d_name_offs,
+                             uint32_t *d_modes, uint8_t *d_types, uint64_t types_cap,
+                             uint64_t *d_type_offs, uint8_t *d_roots, uint64_t *d_sizes,
+                             uint64_t *d_block_sizes, uint32_t *d_status, uint64_t n_cap,
+                             uint64_t counts[5], void *stream);
 
 /* BASELINE config 4 in one call (tree.go:250-320 PostTreeMap over n entries
  * whose blobs are glfs.PostBlob'd, machine.go:64), device-resident: blob i
