@@ -80,6 +80,7 @@ SIGNATURES = {
     "glfsx_clock_probe": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p]),
     "glfsx_one_stats": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p]),
     "glfsx_debug_pass_log": (_INT, [_INT, _VP, _SZ, ctypes.POINTER(ctypes.c_size_t)]),
+    "glfsx_debug_aux_log": (_INT, [_INT, _VP, _SZ, ctypes.POINTER(ctypes.c_size_t)]),
     "glfsx_derive_key": (_INT, [_VP, _SZ, _CP, _VP, _SZ]),
     "glfsx_post": (_INT, [_CP, _VP, _U64, _VP, _VP, _CP]),
     "glfsx_post_batch": (_INT, [_CP, _VP, _U64, _U64, _VP, _VP, _CP]),

@@ -68,6 +68,9 @@ hipError_t clock_probe(int reset, uint64_t out[2]);
 // since the last reset to out, kLaunchRecWords words each; returns how many
 // were launched since then.  reset: empty the log after reading.  No HIP call.
 size_t pass_log(int reset, uint32_t *out, size_t cap);
+// The same for the aux log: the small-blob launches (k_small, k_small_q) and
+// the decrypt launches (k_decrypt_lines, k_decrypt).
+size_t aux_log(int reset, uint32_t *out, size_t cap);
 
 // The second half of launch_post alone: ChaCha20 keyed by the DEK already in
 // bytes [32,64) of each ref slot, ctext store, CID into bytes [0,32).

@@ -1,6 +1,7 @@
-// launch_log.h -- which kernel a bulk launch really ran (the test hook
-// glfsx_debug_pass_log): the record a launch site appends and the bounded
-// log that keeps them.  Plain C++ and a mutex: no HIP, CPU-tested
+// launch_log.h -- which kernel a launch really ran (the test hooks
+// glfsx_debug_pass_log for the bulk passes, glfsx_debug_aux_log for the
+// small-blob and decrypt kernels): the record a launch site appends and the
+// bounded log that keeps them.  Plain C++ and a mutex: no HIP, CPU-tested
 // (tests/c/stream_scratch_test.cpp).
 #pragma once
 #include <stddef.h>
@@ -12,12 +13,24 @@
 
 namespace glfsx {
 
-// Kernel families of the bulk launches.
+// Kernel families of the bulk launches (the pass log) ...
 enum : uint32_t { kLaunchPass = 1, kLaunchQuad = 2, kLaunchPassDc = 3, kLaunchOpen = 4 };
+// ... and of the aux log: k_small, k_small_q, k_decrypt_lines, k_decrypt.
+enum : uint32_t {
+  kLaunchSmall = 5,
+  kLaunchSmallQ = 6,
+  kLaunchDecryptLines = 7,
+  kLaunchDecrypt = 8
+};
+
+// A count as a log word: saturated, never truncated.
+inline uint32_t log_word(uint64_t v) { return v < UINT32_MAX ? uint32_t(v) : UINT32_MAX; }
 
 // One launch: the template arguments of the kernel and the grid.  The
 // selection (launch_plan.h) returns it; the launch site runs and logs it.
 // kLaunchRecWords uint32_t, in this order (include/glfsx.h documents it).
+// The aux families use the same ten words (small_rec, lines_rec,
+// decrypt_rec of launch_plan.h; the word use is in include/glfsx.h).
 struct LaunchRec {
   uint32_t family;      // kLaunchPass ...
   uint32_t g;           // G; k_quad: quads per workgroup

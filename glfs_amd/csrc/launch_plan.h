@@ -33,7 +33,7 @@ constexpr int kPassGs[] = {1, 2, 4, 8, 16, 32, 64};  // k_pass<G, CHACHA, ALIGNE
 constexpr int kQuadQpws[] = {64, 256};                // k_quad<QPW>
 constexpr int kDcGs[] = {1, 2, 4};                    // k_pass_dc<G>
 constexpr int kOpenGs[] = {1, 2, 4, 8};               // k_open<G, ALIGNED, 2>
-constexpr int kSmallGs[] = {1, 2, 4, 8, 16};          // k_small, k_small_q (not logged)
+constexpr int kSmallGs[] = {1, 2, 4, 8, 16};          // k_small, k_small_q (the aux log)
 template <class T, size_t N>
 constexpr bool among(const T (&set)[N], uint32_t x) {
   for (size_t i = 0; i < N; ++i)
@@ -243,12 +243,19 @@ inline bool open_rec(uint64_t n, uint64_t bs, bool salted, bool aligned, int rou
   return true;
 }
 
-// ---- The families outside the log ----
+// ---- The families outside the pass log ----
+// The small-blob kernels (k_small, k_small_q) and the read-side decrypt
+// (k_decrypt_lines, k_decrypt) append to a second log, the aux log
+// (glfsx_debug_aux_log), at their launch sites: small_rec, lines_rec,
+// decrypt_rec below; tests/test_gpu_small_decrypt_matrix.py has a row per
+// instantiation.  The ragged chunk passes (rag_chunk_plan) and the one-shot
+// ladders (oneshot.cpp) stay outside both logs.
 
 struct GridForm {
   uint32_t grid, form;
 };
 // The ragged chunk passes: a workgroup per tile of 256 chunks, at most 2^20.
+// Not logged.
 inline GridForm rag_chunk_plan(uint64_t total, uint32_t latency_wgs) {
   const uint64_t tiles = (total + 255) >> 8;
   return {uint32_t(tiles < (1u << 20) ? tiles : 1u << 20), arx_form(tiles, latency_wgs)};
@@ -284,6 +291,12 @@ inline SmallPlan small_plan(uint64_t n, uint64_t max_len, bool chacha, uint32_t 
 inline uint32_t capped_grid(uint64_t wgs, uint32_t slots) {
   return uint32_t(slots && slots < wgs ? slots : wgs);
 }
+// The aux-log record of a small-blob launch: grid as launched (k_small_q:
+// after capped_grid), n_coarse, items and n saturated.
+inline LaunchRec small_rec(const SmallPlan &p, bool chacha, uint32_t grid, uint64_t n) {
+  return {p.queue ? kLaunchSmallQ : kLaunchSmall, uint32_t(p.g), chacha, 0, p.form, 0, grid,
+          log_word(p.n_coarse), log_word(p.items), log_word(n)};
+}
 
 // launch_decrypt over n blocks of bs bytes (the last last_len).  Whole 4 KiB
 // units go through the line kernel when bs is a multiple of 4096 and both
@@ -315,6 +328,14 @@ inline DecryptPlan decrypt_plan(uint64_t n, uint64_t bs, uint64_t last_len, bool
   p.first_kb = p.units << 6;
   if (p.first_kb < kbs) p.grid = capped_grid((kbs - p.first_kb + 255) / 256, 65536);
   return p;
+}
+// The aux-log records of launch_decrypt's two launches over n blocks.
+inline LaunchRec lines_rec(const DecryptPlan &p, uint64_t n) {
+  return {kLaunchDecryptLines, 0, 1, 1, p.lines.form, p.run_shift, p.lines.grid, p.upb_shift,
+          log_word(p.units), log_word(n)};
+}
+inline LaunchRec decrypt_rec(const DecryptPlan &p, bool aligned, uint64_t n) {
+  return {kLaunchDecrypt, 0, 1, aligned, 0, 0, p.grid, 0, log_word(p.first_kb), log_word(n)};
 }
 
 }  // namespace glfsx

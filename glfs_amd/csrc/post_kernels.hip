@@ -69,6 +69,10 @@ Knobs knobs() {
 // every bulk launch appends the record it was made from.  Never destroyed:
 // a launch on another thread may outlive the process's static destructors.
 LaunchLog &g_launch_log = *new LaunchLog();
+// The aux log (glfsx_debug_aux_log), a log of its own so that the pass log
+// keeps its content: the small-blob launches (launch_small_pass) and the
+// decrypt launches (decrypt_with, the latency-mode posts' keystream leg too).
+LaunchLog &g_aux_log = *new LaunchLog();
 
 // f(integral_constant<int, G>) for the G of Gs (a constexpr array of
 // launch_plan.h) that g equals, hipErrorInvalidValue when it is none.
@@ -278,6 +282,7 @@ hipError_t launch_small_pass(SArgs a, uint64_t max_len, hipStream_t s) {
   return with_g<kSmallGs>(uint32_t(p.g), [&](auto G) {
     if (!p.queue) {
       hipLaunchKernelGGL((k_small<G(), CHACHA, 0>), dim3(uint32_t(p.wgs)), dim3(256), 0, s, a);
+      if (g_aux_log.on()) g_aux_log.append(small_rec(p, CHACHA, uint32_t(p.wgs), a.n));
       return hipGetLastError();
     }
     constexpr int A = CHACHA ? 1 : 2;  // small_plan's form
@@ -285,8 +290,9 @@ hipError_t launch_small_pass(SArgs a, uint64_t max_len, hipStream_t s) {
     uint32_t *ctr, epoch;
     hipError_t e = small_q_get(s, &ctr, &epoch);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_small_q<G(), CHACHA, A>), dim3(capped_grid(p.wgs, slots)), dim3(256), 0,
-                       s, a, ctr, epoch);
+    const uint32_t grid = capped_grid(p.wgs, slots);
+    hipLaunchKernelGGL((k_small_q<G(), CHACHA, A>), dim3(grid), dim3(256), 0, s, a, ctr, epoch);
+    if (g_aux_log.on()) g_aux_log.append(small_rec(p, CHACHA, grid, a.n));
     return hipGetLastError();
   });
 }
@@ -354,8 +360,8 @@ hipError_t decrypt_with(const uint8_t *ctext, uint8_t *ptext, uint64_t n, uint64
   a.last_len = last_len;
   a.n = n;
   a.refs = const_cast<uint8_t *>(refs);
-  const DecryptPlan p =
-      decrypt_plan(n, bs, last_len, ((low_bits(ctext) | low_bits(ptext)) & 15) == 0, latency_wgs);
+  const bool aligned = ((low_bits(ctext) | low_bits(ptext)) & 15) == 0;
+  const DecryptPlan p = decrypt_plan(n, bs, last_len, aligned, latency_wgs);
   if (p.units) {
     if (p.lines.form == 0)
       hipLaunchKernelGGL(k_decrypt_lines<0>, dim3(p.lines.grid), dim3(256), 0, s, a, p.units,
@@ -363,12 +369,14 @@ hipError_t decrypt_with(const uint8_t *ctext, uint8_t *ptext, uint64_t n, uint64
     else
       hipLaunchKernelGGL(k_decrypt_lines<2>, dim3(p.lines.grid), dim3(256), 0, s, a, p.units,
                          p.upb_shift, p.run_shift);
+    if (g_aux_log.on()) g_aux_log.append(lines_rec(p, n));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if (!p.grid) return hipSuccess;
   a.stride = p.first_kb;  // first keystream block left for k_decrypt
   hipLaunchKernelGGL(k_decrypt, dim3(p.grid), dim3(256), 0, s, a);
+  if (g_aux_log.on()) g_aux_log.append(decrypt_rec(p, aligned, n));
   return hipGetLastError();
 }
 
@@ -642,6 +650,11 @@ extern "C" int glfsx_debug_one_timing(int reset, uint64_t out[16]) {
 size_t pass_log(int reset, uint32_t *out, size_t cap) {
   if (!g_launch_log.on()) g_launch_log.enable();
   return g_launch_log.read(reset != 0, out, cap);
+}
+
+size_t aux_log(int reset, uint32_t *out, size_t cap) {
+  if (!g_aux_log.on()) g_aux_log.enable();
+  return g_aux_log.read(reset != 0, out, cap);
 }
 
 hipError_t clock_probe(int reset, uint64_t out[2]) {

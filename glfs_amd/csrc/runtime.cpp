@@ -288,6 +288,13 @@ int glfsx_debug_pass_log(int reset, uint32_t *out, size_t cap, size_t *n) {
   return 0;
 }
 
+int glfsx_debug_aux_log(int reset, uint32_t *out, size_t cap, size_t *n) {
+  if (cap && !out) return fail(GLFSX_E_ARG, "null log buffer");
+  const size_t total = aux_log(reset, out, cap);
+  if (n) *n = total;
+  return 0;
+}
+
 #if GLFSX_WGTIME
 // diagnostic builds only (tools/build_variant.sh): the bulk passes' phase
 // timestamps, 8192 x 16 words

@@ -188,6 +188,39 @@ int glfsx_one_stats(int reset, uint64_t out[3]);
 enum { GLFSX_LOG_PASS = 1, GLFSX_LOG_QUAD = 2, GLFSX_LOG_PASS_DC = 3, GLFSX_LOG_OPEN = 4 };
 int glfsx_debug_pass_log(int reset, uint32_t *out, size_t cap, size_t *n);
 
+/* Test hook (no reference counterpart): the same for the kernels outside the
+ * pass log, in a log of its own (the pass log's content does not change):
+ * the small-blob kernels of glfsx_post_blobs[_device] / glfsx_post_tree_device
+ * and the decrypt kernels of glfsx_decrypt_batch[_device], the Reader, the
+ * composed verified read and the keystream leg of latency-bound posts.  Off
+ * until first called; signature, capacity and semantics as
+ * glfsx_debug_pass_log.  A record is the same GLFSX_PASS_LOG_WORDS words; a
+ * count above UINT32_MAX is stored as UINT32_MAX, never truncated:
+ *   GLFSX_LOG_SMALL (k_small<G, CHACHA, 0>, a lane per blob) and
+ *   GLFSX_LOG_SMALL_Q (k_small_q<G, CHACHA, form>, per-wave work items):
+ *     [1] G, chunks per blob  [2] CHACHA: 0 the DEK pass, 1 the CID pass
+ *     [3] 0  [4] ARX form (k_small 0; k_small_q: DEK 2, CID 1)  [5] 0
+ *     [6] grid launched (k_small_q: after the cap at the resident workgroups)
+ *     [7] n_coarse: items of 64 blobs; the blobs from 64 n_coarse on run as
+ *         fine items of 64 / G (k_small: 0)
+ *     [8] items, coarse and fine (k_small: 0)  [9] n, blobs
+ *   GLFSX_LOG_DECRYPT_LINES (k_decrypt_lines<form>, a wave per 4 KiB unit):
+ *     [1] 0  [2] 1  [3] 1  [4] ARX form, 0 or 2
+ *     [5] run_shift: a wave takes runs of 2^run_shift units  [6] grid
+ *     [7] upb_shift: log2 units per block, 64 when that is no power of two
+ *     [8] units  [9] blocks
+ *   GLFSX_LOG_DECRYPT (k_decrypt, a lane per 64-byte keystream block):
+ *     [1] 0  [2] 1  [3] 1 when both buffers are 16-byte aligned  [4] 0  [5] 0
+ *     [6] grid  [7] 0  [8] first_kb: the first keystream block it takes (the
+ *         ones before it went through k_decrypt_lines)  [9] blocks */
+enum {
+  GLFSX_LOG_SMALL = 5,
+  GLFSX_LOG_SMALL_Q = 6,
+  GLFSX_LOG_DECRYPT_LINES = 7,
+  GLFSX_LOG_DECRYPT = 8
+};
+int glfsx_debug_aux_log(int reset, uint32_t *out, size_t cap, size_t *n);
+
 /* --- primitives -------------------------------------------------------- */
 /* ref.go:152 DeriveKey: BLAKE3 keyed with salt over input (any length),
  * the first out_len bytes of the XOF (any length; blake3.New(len(out), salt)

@@ -5,7 +5,12 @@
 //   launch_plan_sweep                 sweeps shapes, alignments and knob values
 //       and prints one line "K family g chacha aligned form" per distinct
 //       instantiation returned.  Fails unless every record returned is
-//       launchable and every launchable instantiation was returned.
+//       launchable and every launchable instantiation was returned.  Then the
+//       families of the aux log: small_plan over every n in 1..5000 and every
+//       G ("S family G CHACHA form" lines; the set must be kSmallGs x the
+//       dispatcher's forms; k_small_q's item arithmetic covers every blob
+//       once) and decrypt_plan ("D family form" lines; units and keystream
+//       blocks cover the bytes once, no run straddles a block).
 //   launch_plan_sweep FIXTURE         feeds every call recorded in FIXTURE
 //       (scripts/record_launches.py, run at the commit before the selection
 //       moved here) to the pure functions and requires the recorded records.
@@ -123,6 +128,9 @@ static Kernel kernel_of(const LaunchRec &r) {
   return Kernel{r.family, r.g, r.chacha, r.aligned, r.form};
 }
 
+static void sweep_small();
+static void sweep_decrypt();
+
 static int sweep() {
   std::set<Kernel> seen;
   const uint64_t KiB = 1024, MiB = 1024 * KiB;
@@ -168,7 +176,211 @@ static int sweep() {
   for (const Kernel &k : seen)
     printf("K %u %u %u %u %u\n", std::get<0>(k), std::get<1>(k), std::get<2>(k), std::get<3>(k),
            std::get<4>(k));
+  sweep_small();
+  sweep_decrypt();
   return g_failed;
+}
+
+// ---- the families of the aux log: small blobs and the read-side decrypt ----
+
+static void fail_small(const char *what, uint64_t n, uint64_t max_len, bool chacha, uint64_t lat) {
+  fprintf(stderr, "small: %s: n %" PRIu64 " max_len %" PRIu64 " chacha %d lat %" PRIu64 "\n", what,
+          n, max_len, int(chacha), lat);
+  ++g_failed;
+}
+
+// k_small_q's own item arithmetic (small_kernels.h, the first lines of the
+// kernel's body: BPI, fine0, items, and the first blob it hands small_fine),
+// restated here: with the functions shared through launch_plan.h the compiler
+// emitted other code for all ten k_small_q (same registers).  Keep the two in
+// step.  The kernel knows only SArgs::n and SArgs::n_coarse.
+static uint32_t small_bpi(int g) { return g > 1 ? 64u / uint32_t(g) : 64u; }  // BPI
+static uint64_t small_fine0(uint64_t n_coarse) { return n_coarse << 6; }      // fine0
+static uint64_t small_items(uint64_t n, uint64_t n_coarse, uint32_t bpi) {    // items
+  const uint64_t fine0 = small_fine0(n_coarse);
+  return n_coarse + (n > fine0 ? (n - fine0 + bpi - 1) / bpi : 0);
+}
+static uint64_t small_fine_first(uint64_t item, uint64_t n_coarse, uint32_t bpi) {
+  return small_fine0(n_coarse) + (item - n_coarse) * bpi;  // small_fine's b0
+}
+
+// k_small_q's walk over its items (the `while (item < items)` loop,
+// small_blob's `i >= a.n` and small_fine's `valid`): every blob in exactly
+// one item, no item empty, the plan's item count the kernel's own.
+static void check_small_items(const SmallPlan &p, uint64_t n, uint64_t max_len, bool chacha) {
+  const uint32_t bpi = small_bpi(p.g);
+  const uint64_t items = small_items(n, p.n_coarse, bpi), fine0 = small_fine0(p.n_coarse);
+  if (items != p.items) fail_small("items differ from the kernel's", n, max_len, chacha, 0);
+  if (p.wgs != (items + 3) / 4) fail_small("workgroups", n, max_len, chacha, 0);
+  if (fine0 > n) fail_small("coarse items past the end", n, max_len, chacha, 0);
+  if (p.g > 1 && n - fine0 < n / kSmallFineDiv) fail_small("too few fine", n, max_len, chacha, 0);
+  if (p.g == 1 && n - fine0 >= 64) fail_small("G = 1 leaves a whole item", n, max_len, chacha, 0);
+  std::vector<uint8_t> hit(n, 0);
+  for (uint64_t item = 0; item < items; ++item) {
+    // the kernel's branch: a lane per blob of (item << 6 | lane), or a fine item
+    const bool coarse = p.g == 1 || item < p.n_coarse;
+    const uint64_t b0 = coarse ? item << 6 : small_fine_first(item, p.n_coarse, bpi);
+    const uint64_t b1 = b0 + (coarse ? 64 : bpi);
+    if (b0 >= n) fail_small("empty item", n, max_len, chacha, 0);
+    for (uint64_t b = b0; b < b1 && b < n; ++b) ++hit[b];
+  }
+  for (uint64_t b = 0; b < n; ++b)
+    if (hit[b] != 1) {
+      fail_small("a blob in no item or in two", n, max_len, chacha, 0);
+      break;
+    }
+}
+
+using SmallKernel = std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>;  // family G CHACHA form
+
+static void sweep_small() {
+  std::set<SmallKernel> seen, want;
+  // the dispatcher (launch_small_pass): k_small<G, CHACHA, 0>, k_small_q<G, CHACHA, CHACHA ? 1 : 2>
+  for (int g : kSmallGs)
+    for (uint32_t chacha = 0; chacha < 2; ++chacha) {
+      want.insert({kLaunchSmall, uint32_t(g), chacha, 0u});
+      want.insert({kLaunchSmallQ, uint32_t(g), chacha, chacha ? 1u : 2u});
+    }
+  const uint64_t lats[] = {0, 512, 1u << 31};
+  std::vector<uint64_t> ns;
+  for (uint64_t n = 1; n <= 5000; ++n) ns.push_back(n);
+  for (uint64_t n : {65536ull, 131072ull, 131073ull, 400000ull, 1ull << 20}) ns.push_back(n);
+  for (int g : kSmallGs)
+    for (uint64_t max_len : {uint64_t(g) << 10, (uint64_t(g) << 10) - 1, (uint64_t(g) << 9) + 1})
+      for (uint32_t chacha = 0; chacha < 2; ++chacha)
+        for (uint64_t lat : lats)
+          for (uint64_t n : ns) {
+            const SmallPlan p = small_plan(n, max_len, chacha, uint32_t(lat));
+            if (p.g != g) fail_small("G", n, max_len, chacha, lat);
+            if (p.queue != ((n + 255) / 256 > lat)) fail_small("queue", n, max_len, chacha, lat);
+            if (p.wgs == 0 || p.wgs > UINT32_MAX) fail_small("grid", n, max_len, chacha, lat);
+            const LaunchRec r = small_rec(p, chacha, capped_grid(p.wgs, 1280), n);
+            if (r.grid == 0 || r.grid > 1280 || r.n != n || r.fine_div != p.n_coarse ||
+                r.items != p.items)
+              fail_small("record", n, max_len, chacha, lat);
+            seen.insert({r.family, r.g, r.chacha, r.form});
+            if (p.queue)
+              check_small_items(p, n, max_len, chacha);
+            else if (p.items || p.n_coarse || p.form)
+              fail_small("k_small with items", n, max_len, chacha, lat);
+          }
+  if (small_plan(1, 0, false, 0).g != 1 || small_plan(1, 16385, false, 0).g != 0) ++g_failed;
+  // the work-queue row of the GPU matrix: 400 000 blobs of 64 bytes
+  if (small_plan(400000, 64, true, 512).items != 6250) ++g_failed;
+  if (seen != want) {
+    fprintf(stderr, "small: reached %zu instantiations, the dispatcher has %zu\n", seen.size(),
+            want.size());
+    ++g_failed;
+  }
+  for (const SmallKernel &k : seen)
+    printf("S %u %u %u %u\n", std::get<0>(k), std::get<1>(k), std::get<2>(k), std::get<3>(k));
+}
+
+static void fail_decrypt(const char *what, uint64_t n, uint64_t bs, uint64_t last, bool aligned) {
+  fprintf(stderr, "decrypt: %s: n %" PRIu64 " bs %" PRIu64 " last %" PRIu64 " aligned %d\n", what,
+          n, bs, last, int(aligned));
+  ++g_failed;
+}
+
+// decrypt_plan against the kernels' own walk (read_kernels.h): k_decrypt_lines
+// takes run r = units [r << run_shift, min(+ 2^run_shift, units)), the DEK of
+// block j = u0 >> upb_shift (or u0 / upb) for the whole run and the counter
+// (u - j * upb) << 6; k_decrypt the keystream blocks [first_kb, total_kb).
+static void check_decrypt(uint64_t n, uint64_t bs, uint64_t last, bool aligned, uint64_t lat) {
+  const DecryptPlan p = decrypt_plan(n, bs, last, aligned, uint32_t(lat));
+  const uint64_t total = (n - 1) * bs + last, kbs = (total + 63) >> 6;
+  const bool lines = bs % 4096 == 0 && aligned && total >= 4096;
+  if ((p.units != 0) != lines) fail_decrypt("line kernel", n, bs, last, aligned);
+  // units and keystream blocks cover [0, total) exactly once
+  if (p.units << 12 != p.first_kb << 6 || (p.units << 12) > total || p.first_kb > kbs)
+    fail_decrypt("cover", n, bs, last, aligned);
+  if ((p.grid != 0) != (p.first_kb < kbs)) fail_decrypt("k_decrypt launch", n, bs, last, aligned);
+  if (lines && total - (p.units << 12) >= 4096) fail_decrypt("a unit left", n, bs, last, aligned);
+  if (!p.units) {
+    if (p.lines.grid || p.run_shift || p.upb_shift) fail_decrypt("no units", n, bs, last, aligned);
+    return;
+  }
+  const uint64_t upb = bs >> 12;
+  const bool pow2 = (upb & (upb - 1)) == 0;
+  if (pow2 ? (1ull << p.upb_shift) != upb : p.upb_shift != 64)
+    fail_decrypt("upb_shift", n, bs, last, aligned);
+  if (p.upb_shift < 64 ? p.run_shift > p.upb_shift : p.run_shift != 0)
+    fail_decrypt("a run straddles a block", n, bs, last, aligned);
+  const uint64_t runs = (p.units + (1ull << p.run_shift) - 1) >> p.run_shift;
+  if (p.lines.grid == 0 || p.lines.grid > 16384 || p.lines.grid > (runs + 3) / 4)
+    fail_decrypt("grid", n, bs, last, aligned);
+  if (p.run_shift && (p.units >> p.run_shift) < 65536) fail_decrypt("runs", n, bs, last, aligned);
+  if (p.lines.form != (p.lines.grid <= lat ? 0u : 2u)) fail_decrypt("form", n, bs, last, aligned);
+  if (p.units > (1u << 18)) return;
+  uint64_t next = 0;  // the units in run order are 0, 1, 2, ...
+  for (uint64_t run = 0; run < runs; ++run) {
+    const uint64_t u0 = run << p.run_shift;
+    const uint64_t u1 = u0 + (1ull << p.run_shift) < p.units ? u0 + (1ull << p.run_shift) : p.units;
+    const uint64_t j = p.upb_shift < 64 ? u0 >> p.upb_shift : u0 / upb;
+    if (u0 >= u1 || j >= n) fail_decrypt("empty run", n, bs, last, aligned);
+    for (uint64_t u = u0; u < u1; ++u, ++next) {
+      const uint64_t ctr = (u - j * upb) << 6;  // the unit's first counter in block j
+      if (u != next || u / upb != j || j * bs + (ctr << 6) != u << 12 || ctr + 64 > (bs >> 6))
+        fail_decrypt("unit", n, bs, last, aligned);
+    }
+  }
+  if (next != p.units) fail_decrypt("units walked", n, bs, last, aligned);
+}
+
+using DecryptKernel = std::tuple<uint32_t, uint32_t>;  // family form
+
+static void sweep_decrypt() {
+  std::set<DecryptKernel> seen;
+  const uint64_t KiB = 1024, MiB = 1024 * KiB;
+  const uint64_t sizes[] = {64, 128, 4096, 4160, 8192, 12288, 20480, 65536, MiB, 2 * MiB, 3 * MiB};
+  const uint64_t ns[] = {1, 2, 3, 6, 7, 33, 261, 513, 4096, 4097, 43691};
+  const uint64_t lats[] = {0, 512, 1u << 31};
+  for (uint64_t bs : sizes)
+    for (uint64_t n : ns)
+      for (uint64_t last : {uint64_t(1), uint64_t(5), uint64_t(63), uint64_t(64), uint64_t(65),
+                            uint64_t(100), uint64_t(4095), uint64_t(4096), uint64_t(4097),
+                            uint64_t(12365), bs / 2, bs - 1, bs})
+        for (int aligned = 0; aligned < 2; ++aligned)
+          for (uint64_t lat : lats) {
+            if (last == 0 || last > bs) continue;
+            check_decrypt(n, bs, last, aligned != 0, lat);
+            const DecryptPlan p = decrypt_plan(n, bs, last, aligned != 0, uint32_t(lat));
+            if (p.units) {
+              const LaunchRec r = lines_rec(p, n);
+              if (r.split_log2 != p.run_shift || r.fine_div != p.upb_shift || r.items != p.units ||
+                  r.grid != p.lines.grid)
+                fail_decrypt("record", n, bs, last, aligned != 0);
+              seen.insert({r.family, r.form});
+            }
+            if (p.grid) {
+              const LaunchRec r = decrypt_rec(p, aligned != 0, n);
+              if (r.items != p.first_kb || r.grid != p.grid || r.aligned != uint32_t(aligned))
+                fail_decrypt("record", n, bs, last, aligned != 0);
+              seen.insert({r.family, r.form});
+            }
+          }
+  // the rows of the GPU matrix that loop: units, run_shift, upb_shift, grid
+  const struct {
+    uint64_t n, bs, last, units;
+    uint32_t run_shift, upb_shift;
+  } big[] = {{261, MiB, 12365, 66563, 0, 8}, {513, MiB, 12365, 131075, 1, 8},
+             {43691, 12288, 100, 131070, 0, 64}};
+  for (const auto &b : big) {
+    const DecryptPlan p = decrypt_plan(b.n, b.bs, b.last, true, 512);
+    if (p.units != b.units || p.run_shift != b.run_shift || p.upb_shift != b.upb_shift ||
+        p.lines.grid != 16384 || (p.units >> p.run_shift) <= 4ull * p.lines.grid || p.grid != 1)
+      fail_decrypt("a looping row", b.n, b.bs, b.last, true);
+  }
+  if (log_word(UINT32_MAX - 1ull) != UINT32_MAX - 1 || log_word(UINT32_MAX) != UINT32_MAX ||
+      log_word(1ull << 32) != UINT32_MAX || log_word(~0ull) != UINT32_MAX)
+    ++g_failed;
+  const std::set<DecryptKernel> want = {
+      {kLaunchDecryptLines, 0u}, {kLaunchDecryptLines, 2u}, {kLaunchDecrypt, 0u}};
+  if (seen != want) {
+    fprintf(stderr, "decrypt: reached %zu kernels of 3\n", seen.size());
+    ++g_failed;
+  }
+  for (const DecryptKernel &k : seen) printf("D %u %u\n", std::get<0>(k), std::get<1>(k));
 }
 
 static int replay(const char *path) {
