@@ -1,6 +1,7 @@
 // blobs.cpp -- many blobs in one call (post_blobs) and a tree with its
 // blobs (post_tree), from host or device memory.
 #include "host.h"
+#include "ragged_groups.h"
 
 using namespace glfsx;
 using namespace glfsx::host;
@@ -19,19 +20,11 @@ int glfsx_post_blobs_device(uint64_t block_size, const uint8_t *salt,
   hipStream_t s = pick_stream(c, stream);
   Salts salts;
   if (int e = derive_salts(c, salt, &salts)) return e;
-  SmallJob j{};
-  j.src = static_cast<const uint8_t *>(d_data);
-  j.ctext = static_cast<uint8_t *>(d_ctext);
-  j.offs = d_offsets;
-  j.lens = d_lengths;
-  j.n = n;
-  j.max_len = max_len;
-  j.refs = static_cast<uint8_t *>(d_roots);
-  set_keys(j, salts, cid_key);
   // blobs of <= min(16 KiB, block_size): one lane each (k_small skips the
   // others; a blob longer than its block size has several blocks)
   const uint64_t small_max = small_max_for(block_size);
-  j.small_max = small_max;
+  SmallJob j = small_job(d_data, d_ctext, d_offsets, d_lengths, n, max_len, small_max, d_roots);
+  set_keys(j, salts, cid_key);
   HIP_TRY(launch_post_small(j, s));
   if (max_len <= small_max) return 0;
   // larger single-block blobs (the caller said some may exceed 16 KiB), up
@@ -39,15 +32,8 @@ int glfsx_post_blobs_device(uint64_t block_size, const uint8_t *salt,
   // (the root is post(rawSalt, blob), blob.go:190-193)
   const uint64_t rag_max = std::min(block_size, kMaxRaggedLen);
   if (rag_max > small_max) {  // (not at block sizes of 16 KiB and less)
-    RaggedJob rj{};
-    rj.src = j.src;
-    rj.ctext = j.ctext;
-    rj.offs = d_offsets;
-    rj.lens = d_lengths;
-    rj.n = n;
-    rj.lo = small_max;
-    rj.hi = std::min(max_len, rag_max);
-    rj.refs = j.refs;
+    RaggedJob rj = ragged_job(d_data, d_ctext, d_offsets, d_lengths, n, small_max,
+                              std::min(max_len, rag_max), d_roots);
     set_keys(rj, salts.raw, cid_key);
     HIP_TRY(launch_post_ragged(rj, s));
   }
@@ -92,15 +78,7 @@ int glfsx_post_ragged_device(const uint8_t salt[32], const uint8_t *cid_key,
   Ctx *c;
   if (int e = ctx_get(&c)) return e;
   hipStream_t s = pick_stream(c, stream);
-  RaggedJob rj{};
-  rj.src = static_cast<const uint8_t *>(d_data);
-  rj.ctext = static_cast<uint8_t *>(d_ctext);
-  rj.offs = d_offsets;
-  rj.lens = d_lengths;
-  rj.n = n;
-  rj.lo = kRaggedAll;
-  rj.hi = max_len;
-  rj.refs = static_cast<uint8_t *>(d_refs);
+  RaggedJob rj = ragged_job(d_data, d_ctext, d_offsets, d_lengths, n, kRaggedAll, max_len, d_refs);
   set_keys(rj, salt, cid_key);
   HIP_TRY(launch_post_ragged(rj, s));
   return 0;
@@ -225,51 +203,30 @@ int post_small_groups(Ctx *c, uint64_t bs, const uint8_t *salt, const uint8_t *c
       g.loff.assign(m, 0);
       uint64_t *lo = reinterpret_cast<uint64_t *>(g.h_meta.p), *ll = lo + m;
       // pack, copying each run of blobs that are contiguous in `data` at once
-      uint64_t o = 0, run_src = 0, run_dst = 0, run_len = 0;
+      uint64_t o = 0;
       for (uint64_t j = 0; j < m; ++j) {
-        const uint64_t idx = i + j, len = lengths[idx];
+        const uint64_t len = lengths[i + j];
         const bool here = len <= med_max;
         if (here) o = slot_offset(o, len, small_max);
         lo[j] = here ? o : 0;
-        ll[j] = here ? len : ~0ull;  // skipped by both posts
+        ll[j] = here ? len : kRaggedAbsent;  // skipped by both posts
         g.loff[j] = lo[j];
-        if (!here || len == 0) continue;
-        if (run_len && offsets[idx] == run_src + run_len && o == run_dst + run_len) {
-          run_len += len;
-        } else {
-          if (run_len) par_memcpy(g.h_in.u8() + run_dst, data + run_src, run_len);
-          run_src = offsets[idx];
-          run_dst = o;
-          run_len = len;
-        }
-        o += len;
+        if (here) o += len;
       }
-      if (run_len) par_memcpy(g.h_in.u8() + run_dst, data + run_src, run_len);
+      ragged_runs(offsets + i, lo, ll, m, [&](uint64_t src, uint64_t dst, uint64_t len) {
+        par_memcpy(g.h_in.u8() + dst, data + src, len);
+      });
       if (bytes) HIP_TRY(hipMemcpyAsync(g.d_in.p, g.h_in.p, bytes, hipMemcpyHostToDevice, c->s_up));
       HIP_TRY(hipMemcpyAsync(g.d_meta.p, g.h_meta.p, 16 * m, hipMemcpyHostToDevice, c->s_up));
       HIP_TRY(hipEventRecord(g.up, c->s_up));
       HIP_TRY(hipStreamWaitEvent(c->stream, g.up, 0));
-      SmallJob j{};
-      j.src = g.d_in.u8();
-      j.ctext = g.d_ct.u8();
-      j.offs = reinterpret_cast<const uint64_t *>(g.d_meta.p);
-      j.lens = j.offs + m;
-      j.n = m;
-      j.max_len = max_len;
-      j.small_max = small_max;
-      j.refs = g.d_refs.u8();
+      const uint64_t *d_lo = reinterpret_cast<const uint64_t *>(g.d_meta.p);
+      SmallJob j = small_job(g.d_in.p, g.d_ct.p, d_lo, d_lo + m, m, max_len, small_max, g.d_refs.p);
       set_keys(j, salts, cid_key);
       HIP_TRY(launch_post_small(j, c->stream));
       if (max_med) {  // blobs above small_max (k_small skipped them)
-        RaggedJob rj{};
-        rj.src = j.src;
-        rj.ctext = j.ctext;
-        rj.offs = j.offs;
-        rj.lens = j.lens;
-        rj.n = m;
-        rj.lo = small_max;
-        rj.hi = max_med;
-        rj.refs = j.refs;
+        RaggedJob rj = ragged_job(g.d_in.p, g.d_ct.p, d_lo, d_lo + m, m, small_max, max_med,
+                                  g.d_refs.p);
         set_keys(rj, salts.raw, cid_key);
         HIP_TRY(launch_post_ragged(rj, c->stream));
       }
@@ -411,20 +368,8 @@ int post_tree_device_impl(uint64_t n, uint64_t blob_bs, const uint8_t *blob_salt
   const uint64_t words = n + wgs + 1;
   if (int e = c->d_tree.ensure(8 * (words + n))) return e;
   if (int e = c->h_tree.ensure(8 * (wgs + 1))) return e;
-  TreeJob tj{};
-  tj.n = n;
-  tj.names = d_names;
-  tj.name_offs = d_name_offs;
-  tj.modes = d_modes;
-  tj.types = d_types;
-  tj.type_offs = d_type_offs;
-  tj.roots = static_cast<const uint8_t *>(d_roots);
-  tj.sizes = d_lengths;
-  tj.block_sizes = d_block_sizes;
-  tj.scratch = reinterpret_cast<uint64_t *>(c->d_tree.p);
-  tj.total = tj.scratch + words - 1;
-  tj.out = static_cast<uint8_t *>(d_lines);
-  tj.cap = lines_cap;
+  TreeJob tj = tree_job(n, d_names, d_name_offs, d_modes, d_types, d_type_offs, d_roots,
+                        d_lengths, d_block_sizes, c->d_tree.p, words, d_lines, lines_cap);
   tj.hex_pos = tj.scratch + words;  // where each root's digits go
   tj.prio = 1;                      // beside the DEK pass: raised issue priority
   // the prefix stores the exclusive prefixes and the total in the pinned
@@ -434,15 +379,8 @@ int post_tree_device_impl(uint64_t n, uint64_t blob_bs, const uint8_t *blob_salt
   // B's work comes after everything already on A
   HIP_TRY(hipEventRecord(ev_before, A));
   HIP_TRY(hipStreamWaitEvent(B, ev_before, 0));
-  SmallJob sj{};
-  sj.src = static_cast<const uint8_t *>(d_data);
-  sj.ctext = static_cast<uint8_t *>(d_ctext);
-  sj.max_len = max_len;
-  sj.small_max = small_max_for(blob_bs);
-  sj.offs = d_offsets;
-  sj.lens = d_lengths;
-  sj.n = n;
-  sj.refs = static_cast<uint8_t *>(d_roots);
+  SmallJob sj = small_job(d_data, d_ctext, d_offsets, d_lengths, n, max_len,
+                          small_max_for(blob_bs), d_roots);
   set_keys(sj, bsalts, cid_key);
   sj.passes = 1;  // the DEK pass: the critical path, queued first
   HIP_TRY(launch_post_small(sj, A));
@@ -525,21 +463,9 @@ int glfsx_tree_encode_device(uint64_t n, const uint8_t *d_names,
   const uint64_t words = n + (n + kTreeWG - 1) / kTreeWG + 1;
   if (int e = c->d_tree.ensure(8 * words)) return e;
   if (int e = c->h_small.ensure(64)) return e;
-  TreeJob j{};
-  j.n = n;
-  j.names = d_names;
-  j.name_offs = d_name_offs;
-  j.modes = d_modes;
-  j.types = d_types;
-  j.type_offs = d_type_offs;
-  j.roots = d_roots;
-  j.sizes = d_sizes;
-  j.block_sizes = d_block_sizes;
-  j.scratch = reinterpret_cast<uint64_t *>(c->d_tree.p);
-  j.total = j.scratch + words - 1;
+  TreeJob j = tree_job(n, d_names, d_name_offs, d_modes, d_types, d_type_offs, d_roots, d_sizes,
+                       d_block_sizes, c->d_tree.p, words, d_out, d_out ? out_cap : 0);
   j.line_ends = d_line_ends;
-  j.out = static_cast<uint8_t *>(d_out);
-  j.cap = d_out ? out_cap : 0;
   HIP_TRY(launch_tree_encode(j, s));
   HIP_TRY(hipMemcpyAsync(c->h_small.p, j.total, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(stream_wait(s));

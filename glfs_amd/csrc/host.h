@@ -6,6 +6,8 @@
 // kernels of post_kernels.hip; the host units only stage bytes, sequence
 // launches and keep the reference's Writer bookkeeping (blob.go:71-206); one
 // unit per family (DESIGN.md "Host language").  Internal: hidden visibility.
+// writer_book.h: that bookkeeping (fill cursor, index stack) as pure state.
+// ragged_groups.h: a batch's groups and the run copier (ragged_runs).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -323,6 +325,108 @@ inline void set_keys(SmallJob &j, const Salts &s, const uint8_t *cid_key) {
   words_from_key(j.raw_salt, s.raw);
   words_from_key(j.index_salt, s.index);
   set_cid_key(j, cid_key);
+}
+// The read side's keys (OpenJob, OpenRaggedJob): salt null = the CID check only.
+template <class J>
+void open_keys(J &j, const uint8_t *salt, const uint8_t *cid_key) {
+  j.salted = salt != nullptr;
+  if (salt) words_from_key(j.salt, salt);
+  set_cid_key(j, cid_key);
+}
+// n blobs, blob i the lens[i] bytes at offs[i] of src (device arrays), its
+// root to refs + 64 i: those of at most small_max bytes, one lane each.
+inline SmallJob small_job(const void *src, void *ctext, const uint64_t *offs,
+                          const uint64_t *lens, uint64_t n, uint64_t max_len,
+                          uint64_t small_max, void *refs) {
+  SmallJob j{};
+  j.src = static_cast<const uint8_t *>(src);
+  j.ctext = static_cast<uint8_t *>(ctext);
+  j.offs = offs;
+  j.lens = lens;
+  j.n = n;
+  j.max_len = max_len;
+  j.small_max = small_max;
+  j.refs = static_cast<uint8_t *>(refs);
+  return j;
+}
+// The same layout, the messages of lo < lens[i] <= hi bytes in throughput form.
+inline RaggedJob ragged_job(const void *src, void *ctext, const uint64_t *offs,
+                            const uint64_t *lens, uint64_t n, uint64_t lo, uint64_t hi,
+                            void *refs) {
+  RaggedJob j{};
+  j.src = static_cast<const uint8_t *>(src);
+  j.ctext = static_cast<uint8_t *>(ctext);
+  j.offs = offs;
+  j.lens = lens;
+  j.n = n;
+  j.lo = lo;
+  j.hi = hi;
+  j.refs = static_cast<uint8_t *>(refs);
+  return j;
+}
+// The verified read of ceil(total / bs) blocks of bs bytes back to back at
+// ctext, the last one short (total 0: one empty block).
+inline OpenJob open_job(const void *ctext, void *ptext, uint64_t total, uint64_t bs,
+                        const void *refs, uint32_t *status) {
+  OpenJob j{};
+  j.ctext = static_cast<const uint8_t *>(ctext);
+  j.ptext = static_cast<uint8_t *>(ptext);
+  j.n = total ? (total + bs - 1) / bs : 1;
+  j.bs = bs;
+  j.last_len = total - (j.n - 1) * bs;
+  j.refs = static_cast<const uint8_t *>(refs);
+  j.status = status;
+  return j;
+}
+// The same of n messages, message i the lens[i] bytes at offs[i] of ctext.
+inline OpenRaggedJob open_ragged_job(const void *ctext, void *ptext, const uint64_t *offs,
+                                     const uint64_t *lens, uint64_t n, uint64_t max_len,
+                                     const void *refs, uint32_t *status) {
+  OpenRaggedJob j{};
+  j.ctext = static_cast<const uint8_t *>(ctext);
+  j.ptext = static_cast<uint8_t *>(ptext);
+  j.offs = offs;
+  j.lens = lens;
+  j.n = n;
+  j.max_len = max_len;
+  j.refs = static_cast<const uint8_t *>(refs);
+  j.status = status;
+  return j;
+}
+// The columns of n tree entries, the `words` words of scratch their lines'
+// layout takes (the total in the last one) and the cap bytes at out.
+inline TreeJob tree_job(uint64_t n, const uint8_t *names, const uint64_t *name_offs,
+                        const uint32_t *modes, const uint8_t *types, const uint64_t *type_offs,
+                        const void *roots, const uint64_t *sizes, const uint64_t *block_sizes,
+                        void *scratch, uint64_t words, void *out, uint64_t cap) {
+  TreeJob j{};
+  j.n = n;
+  j.names = names;
+  j.name_offs = name_offs;
+  j.modes = modes;
+  j.types = types;
+  j.type_offs = type_offs;
+  j.roots = static_cast<const uint8_t *>(roots);
+  j.sizes = sizes;
+  j.block_sizes = block_sizes;
+  j.scratch = static_cast<uint64_t *>(scratch);
+  j.total = j.scratch + words - 1;
+  j.out = static_cast<uint8_t *>(out);
+  j.cap = cap;
+  return j;
+}
+
+// The text of a failed verified read: "failed its CID and DEK checks", ...
+inline const char *failed_checks(uint32_t status) {
+  return status == 3 ? "failed its CID and DEK checks"
+                     : status == 1 ? "failed its CID check" : "failed its DEK check";
+}
+// GLFSX_E_CORRUPT for a batch of n `what`s (block, message), bad of them bad.
+inline int corrupt_fail(const char *what, uint64_t first_bad, uint64_t n, uint32_t status,
+                        uint64_t bad) {
+  return fail(GLFSX_E_CORRUPT, "%s %llu of %llu %s (%llu bad in all)", what,
+              (unsigned long long)first_bad, (unsigned long long)n, failed_checks(status),
+              (unsigned long long)bad);
 }
 
 // ---- oneshot.cpp ----

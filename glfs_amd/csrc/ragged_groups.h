@@ -47,4 +47,29 @@ inline void ragged_groups(const uint64_t *lens, uint64_t n, uint64_t cap,
   }
 }
 
+// The copies between a batch of messages and its staging: message j lies at
+// src_off[j] of the caller's memory and at stage_off[j] of the staging,
+// lens[j] bytes.  run(src, stage, len) is called once per maximal run of
+// messages contiguous on both sides, in order; messages of length 0 or
+// kRaggedAbsent (not staged at all) are skipped.
+constexpr uint64_t kRaggedAbsent = ~0ull;
+template <class Run>
+void ragged_runs(const uint64_t *src_off, const uint64_t *stage_off, const uint64_t *lens,
+                 uint64_t n, Run &&run) {
+  uint64_t run_src = 0, run_dst = 0, run_len = 0;
+  for (uint64_t j = 0; j < n; ++j) {
+    const uint64_t len = lens[j];
+    if (len == 0 || len == kRaggedAbsent) continue;
+    if (run_len && src_off[j] == run_src + run_len && stage_off[j] == run_dst + run_len) {
+      run_len += len;
+    } else {
+      if (run_len) run(run_src, run_dst, run_len);
+      run_src = src_off[j];
+      run_dst = stage_off[j];
+      run_len = len;
+    }
+  }
+  if (run_len) run(run_src, run_dst, run_len);
+}
+
 }  // namespace glfsx

@@ -13,8 +13,8 @@ namespace {
 // What a slab of the host pipeline runs: a plain decrypt (open == nullptr),
 // or the verified read with these keys (ptext nullable then).
 struct SlabOpen {
-  OpenJob keys;          // salt, cid_key, salted, cid_keyed
-  uint32_t *status_out;  // nullable
+  const uint8_t *salt, *cid_key;  // as open_keys takes them
+  uint32_t *status_out;           // nullable
   uint64_t n_bad = 0, first_bad = 0;
   uint32_t first_status = 0;
 };
@@ -90,20 +90,14 @@ int slab_pipeline(Ctx *c, const void *ctext, uint64_t total, uint64_t block_size
                            hipMemcpyHostToDevice, s_up));
     HIP_TRY(hipEventRecord(sl.up, s_up));
     HIP_TRY(hipStreamWaitEvent(c->stream, sl.up, 0));
-    const uint64_t last_len = sl.bytes - (sl.nb - 1) * block_size;
     if (open) {
-      OpenJob job = open->keys;
-      job.ctext = sl.d_in.u8();
-      job.ptext = ptext ? sl.d_out.u8() : nullptr;
-      job.n = sl.nb;
-      job.bs = block_size;
-      job.last_len = last_len;
-      job.refs = sl.d_refs.u8();
-      job.status = static_cast<uint32_t *>(sl.d_status.p);
+      OpenJob job = open_job(sl.d_in.p, ptext ? sl.d_out.p : nullptr, sl.bytes, block_size,
+                             sl.d_refs.p, static_cast<uint32_t *>(sl.d_status.p));
+      open_keys(job, open->salt, open->cid_key);
       HIP_TRY(launch_open(job, c->stream));
     } else {
-      HIP_TRY(launch_decrypt(sl.d_in.u8(), sl.d_out.u8(), sl.nb, block_size, last_len,
-                             sl.d_refs.u8(), c->stream));
+      HIP_TRY(launch_decrypt(sl.d_in.u8(), sl.d_out.u8(), sl.nb, block_size,
+                             sl.bytes - (sl.nb - 1) * block_size, sl.d_refs.u8(), c->stream));
     }
     HIP_TRY(hipEventRecord(sl.up, c->stream));
     HIP_TRY(hipStreamWaitEvent(s_dn, sl.up, 0));
@@ -118,13 +112,6 @@ int slab_pipeline(Ctx *c, const void *ctext, uint64_t total, uint64_t block_size
   for (int i = 0; i < 2; ++i, k ^= 1)
     if (int e = finish(slots[k])) return bail(e);
   return 0;
-}
-
-template <class J>  // OpenJob, OpenRaggedJob
-void open_keys(J &j, const uint8_t *salt, const uint8_t *cid_key) {
-  j.salted = salt != nullptr;
-  if (salt) words_from_key(j.salt, salt);
-  set_cid_key(j, cid_key);
 }
 
 int open_check_args(const void *ctext, const void *refs, const void *status, bool need_status,
@@ -179,15 +166,8 @@ int glfsx_open_batch_device(const uint8_t *salt, const uint8_t *cid_key,
   if (int e = open_check_args(d_ctext, d_refs, d_status, true, block_size)) return e;
   Ctx *c;
   if (int e = ctx_get(&c)) return e;
-  OpenJob job{};
+  OpenJob job = open_job(d_ctext, d_ptext, total, block_size, d_refs, d_status);
   open_keys(job, salt, cid_key);
-  job.ctext = static_cast<const uint8_t *>(d_ctext);
-  job.ptext = static_cast<uint8_t *>(d_ptext);
-  job.n = (total + block_size - 1) / block_size;
-  job.bs = block_size;
-  job.last_len = total - (job.n - 1) * block_size;
-  job.refs = static_cast<const uint8_t *>(d_refs);
-  job.status = d_status;
   HIP_TRY(launch_open(job, pick_stream(c, stream)));
   return 0;
 }
@@ -200,17 +180,12 @@ int glfsx_open_batch(const uint8_t *salt, const uint8_t *cid_key, const void *ct
   if (int e = open_check_args(ctext, refs, status_out, false, block_size)) return e;
   Ctx *c;
   if (int e = ctx_get(&c)) return e;
-  SlabOpen op{};
-  open_keys(op.keys, salt, cid_key);
-  op.status_out = status_out;
+  SlabOpen op{salt, cid_key, status_out};
   if (int e = slab_pipeline(c, ctext, total, block_size, refs, ptext, &op)) return e;
   if (n_bad) *n_bad = op.n_bad;
   if (op.n_bad == 0) return 0;
-  return fail(GLFSX_E_CORRUPT, "block %llu of %llu failed its %s check%s (%llu bad in all)",
-              (unsigned long long)op.first_bad,
-              (unsigned long long)((total + block_size - 1) / block_size),
-              op.first_status == 3 ? "CID and DEK" : op.first_status == 1 ? "CID" : "DEK",
-              op.first_status == 3 ? "s" : "", (unsigned long long)op.n_bad);
+  return corrupt_fail("block", op.first_bad, (total + block_size - 1) / block_size,
+                      op.first_status, op.n_bad);
 }
 
 int glfsx_set_open_route(int route) { return set_open_route(route); }
@@ -240,15 +215,9 @@ int glfsx_open(const uint8_t *salt, const uint8_t *cid_key, const uint8_t ref[64
     if (int e = c->d_refs.ensure(128)) return e;
     if (n) HIP_TRY(hipMemcpyAsync(c->d_in.p, ctext, n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_refs.p, ref, 64, hipMemcpyHostToDevice, c->stream));
-    OpenJob job{};
+    OpenJob job = open_job(c->d_in.p, ptext ? c->d_ct.p : nullptr, n, bs, c->d_refs.p,
+                           reinterpret_cast<uint32_t *>(c->d_refs.u8() + 64));
     open_keys(job, salt, cid_key);
-    job.ctext = c->d_in.u8();
-    job.ptext = ptext ? c->d_ct.u8() : nullptr;
-    job.n = 1;
-    job.bs = bs;
-    job.last_len = n;
-    job.refs = c->d_refs.u8();
-    job.status = reinterpret_cast<uint32_t *>(c->d_refs.u8() + 64);
     HIP_TRY(launch_open(job, c->stream));
     if (ptext && n)
       HIP_TRY(hipMemcpyAsync(ptext, c->d_ct.p, n, hipMemcpyDeviceToHost, c->stream));
@@ -259,8 +228,7 @@ int glfsx_open(const uint8_t *salt, const uint8_t *cid_key, const uint8_t ref[64
   if (!status) return 0;
   char hex[65];
   for (int i = 0; i < 32; ++i) snprintf(hex + 2 * i, 3, "%02x", ref[i]);
-  return fail(GLFSX_E_CORRUPT, "blob %s failed its %s check%s", hex,
-              status == 3 ? "CID and DEK" : status == 1 ? "CID" : "DEK", status == 3 ? "s" : "");
+  return fail(GLFSX_E_CORRUPT, "blob %s %s", hex, failed_checks(status));
 }
 
 int glfsx_open_ragged_device(const uint8_t *salt, const uint8_t *cid_key,
@@ -278,16 +246,9 @@ int glfsx_open_ragged_device(const uint8_t *salt, const uint8_t *cid_key,
   if (!d_offsets || !d_lengths) return fail(GLFSX_E_ARG, "null argument");
   Ctx *c;
   if (int e = ctx_get(&c)) return e;
-  OpenRaggedJob job{};
+  OpenRaggedJob job =
+      open_ragged_job(d_ctext, d_ptext, d_offsets, d_lengths, n, max_len, d_refs, d_status);
   open_keys(job, salt, cid_key);
-  job.ctext = static_cast<const uint8_t *>(d_ctext);
-  job.ptext = static_cast<uint8_t *>(d_ptext);
-  job.offs = d_offsets;
-  job.lens = d_lengths;
-  job.n = n;
-  job.max_len = max_len;
-  job.refs = static_cast<const uint8_t *>(d_refs);
-  job.status = d_status;
   HIP_TRY(launch_open_ragged(job, pick_stream(c, stream)));
   return 0;
 }
@@ -309,8 +270,6 @@ int glfsx_open_blobs(const uint8_t *salt, const uint8_t *cid_key, const void *ct
   ragged_groups(lengths, n, kRaggedGroupBytes, &groups, &soff);
   Ctx *c;
   if (int e = ctx_get(&c)) return e;
-  OpenRaggedJob keys{};
-  open_keys(keys, salt, cid_key);
   const uint8_t *src = static_cast<const uint8_t *>(ctext);
   uint8_t *dst = static_cast<uint8_t *>(ptext);
   // The groups one after the other through the thread's first pooled slot:
@@ -328,37 +287,22 @@ int glfsx_open_blobs(const uint8_t *salt, const uint8_t *cid_key, const void *ct
     if (int e = g.h_refs.ensure(64 * m)) return e;
     if (int e = g.d_refs.ensure(64 * m)) return e;
     uint64_t *lo = reinterpret_cast<uint64_t *>(g.h_meta.p), *ll = lo + m;
+    memcpy(lo, &soff[grp.i0], 8 * m);
+    memcpy(ll, lengths + grp.i0, 8 * m);
     // gather, copying each run of messages contiguous on both sides at once
-    uint64_t run_src = 0, run_dst = 0, run_len = 0;
-    for (uint64_t j = 0; j < m; ++j) {
-      const uint64_t i = grp.i0 + j, len = lengths[i];
-      lo[j] = soff[i];
-      ll[j] = len;
-      if (len == 0) continue;
-      if (run_len && offsets[i] == run_src + run_len && soff[i] == run_dst + run_len) {
-        run_len += len;
-      } else {
-        if (run_len) par_memcpy(g.h_in.u8() + run_dst, src + run_src, run_len);
-        run_src = offsets[i];
-        run_dst = soff[i];
-        run_len = len;
-      }
-    }
-    if (run_len) par_memcpy(g.h_in.u8() + run_dst, src + run_src, run_len);
+    ragged_runs(offsets + grp.i0, lo, ll, m, [&](uint64_t s, uint64_t d, uint64_t len) {
+      par_memcpy(g.h_in.u8() + d, src + s, len);
+    });
     memcpy(g.h_refs.p, refs + 64 * grp.i0, 64 * m);
     if (grp.bytes)
       HIP_TRY(hipMemcpyAsync(g.d_in.p, g.h_in.p, grp.bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(g.d_meta.p, g.h_meta.p, 16 * m, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(g.d_refs.p, g.h_refs.p, 64 * m, hipMemcpyHostToDevice, c->stream));
-    OpenRaggedJob job = keys;
-    job.ctext = g.d_in.u8();
-    job.ptext = ptext ? g.d_in.u8() : nullptr;  // in place: staged messages are disjoint
-    job.offs = reinterpret_cast<const uint64_t *>(g.d_meta.p);
-    job.lens = job.offs + m;
-    job.n = m;
-    job.max_len = max_len;
-    job.refs = g.d_refs.u8();
-    job.status = reinterpret_cast<uint32_t *>(g.d_meta.u8() + 16 * m);
+    const uint64_t *d_lo = reinterpret_cast<const uint64_t *>(g.d_meta.p);
+    OpenRaggedJob job =  // in place: staged messages are disjoint
+        open_ragged_job(g.d_in.p, ptext ? g.d_in.p : nullptr, d_lo, d_lo + m, m, max_len,
+                        g.d_refs.p, reinterpret_cast<uint32_t *>(g.d_meta.u8() + 16 * m));
+    open_keys(job, salt, cid_key);
     HIP_TRY(launch_open_ragged(job, c->stream));
     if (ptext && grp.bytes)
       HIP_TRY(hipMemcpyAsync(g.h_in.p, g.d_in.p, grp.bytes, hipMemcpyDeviceToHost, c->stream));
@@ -372,22 +316,10 @@ int glfsx_open_blobs(const uint8_t *salt, const uint8_t *cid_key, const void *ct
         first_bad = grp.i0 + j;
         first_status = st[j];
       }
-    if (ptext) {  // scatter, by the same runs
-      run_len = 0;
-      for (uint64_t j = 0; j < m; ++j) {
-        const uint64_t i = grp.i0 + j, len = lengths[i];
-        if (len == 0) continue;
-        if (run_len && offsets[i] == run_src + run_len && soff[i] == run_dst + run_len) {
-          run_len += len;
-        } else {
-          if (run_len) par_memcpy(dst + run_src, g.h_in.u8() + run_dst, run_len);
-          run_src = offsets[i];
-          run_dst = soff[i];
-          run_len = len;
-        }
-      }
-      if (run_len) par_memcpy(dst + run_src, g.h_in.u8() + run_dst, run_len);
-    }
+    if (ptext)  // scatter, by the same runs
+      ragged_runs(offsets + grp.i0, lo, ll, m, [&](uint64_t s, uint64_t d, uint64_t len) {
+        par_memcpy(dst + s, g.h_in.u8() + d, len);
+      });
     return 0;
   };
   for (const RaggedGroup &grp : groups)
@@ -397,10 +329,7 @@ int glfsx_open_blobs(const uint8_t *salt, const uint8_t *cid_key, const void *ct
     }
   if (n_bad) *n_bad = bad;
   if (bad == 0) return 0;
-  return fail(GLFSX_E_CORRUPT, "message %llu of %llu failed its %s check%s (%llu bad in all)",
-              (unsigned long long)first_bad, (unsigned long long)n,
-              first_status == 3 ? "CID and DEK" : first_status == 1 ? "CID" : "DEK",
-              first_status == 3 ? "s" : "", (unsigned long long)bad);
+  return corrupt_fail("message", first_bad, n, first_status, bad);
 }
 
 }  // extern "C"

@@ -42,35 +42,31 @@ int post_one(glfsx_writer *w, int kind, const uint8_t salt[32],
   return deliver(w->post, w->post_ctx, kind, ref, o.h_ct.p, n);
 }
 
-// blob.go:165-182
-// A level's node holds only its refs (64 B each); it is zero padded to bs
-// bytes when posted (index.go:33-38), so a one-block blob never touches a
-// bs-byte buffer.
-int post_node(glfsx_writer *w, size_t i, uint8_t r[64]) {
-  std::vector<uint8_t> &v = w->indexes[i];
-  int e;
-  if (w->bs <= kMaxMedLen) {  // the kernel reads the rest as zero
-    e = post_one(w, 1, w->salts.index, v.data(), w->bs, r, false, nullptr, v.size());
-  } else {
-    v.resize(w->bs, 0);
-    e = post_one(w, 1, w->salts.index, v.data(), w->bs, r);
-  }
-  v.clear();
-  return e;
+// The index stack's post (writer_book.h; blob.go:165-206): an index node of
+// len bytes, its refs in the first `present` of them, or the empty blob's
+// node (len 0).
+auto node_poster(glfsx_writer *w) {
+  return [w](const uint8_t *refs, uint64_t present, uint64_t len, uint8_t out[64]) -> int {
+    if (len <= kMaxMedLen)  // the kernel reads the rest as zero
+      return post_one(w, 1, w->salts.index, refs, len, out, false, nullptr, present);
+    w->node.assign(len, 0);
+    memcpy(w->node.data(), refs, present);
+    return post_one(w, 1, w->salts.index, w->node.data(), len, out);
+  };
 }
 
-int add_ref(glfsx_writer *w, size_t i, const uint8_t ref[64]) {
-  if (w->indexes.size() <= i) {
-    w->indexes.emplace_back();
-    w->counts.push_back(0);
-  }
-  w->indexes[i].insert(w->indexes[i].end(), ref, ref + 64);
-  w->counts[i]++;
-  if (w->counts[i] < w->bf) return 0;
-  uint8_t r2[64];
-  if (int e = post_node(w, i, r2)) return e;
-  w->counts[i] = 0;
-  return add_ref(w, i + 1, r2);
+// The Writer's half of postBuf (blob.go:152-163) for a block the GPU has
+// posted: addRef, then the size.
+int account_block(glfsx_writer *w, const uint8_t ref[64], uint64_t len) {
+  if (int e = w->index.add(ref, node_poster(w))) return e;
+  w->size += len;
+  return 0;
+}
+
+// The same with its Post: deliver -> addRef -> size.
+int replay_block(glfsx_writer *w, const uint8_t ref[64], const void *ctext, uint64_t len) {
+  if (int e = deliver(w->post, w->post_ctx, 0, ref, ctext, len)) return e;
+  return account_block(w, ref, len);
 }
 
 // A one-launch split post on the hash stream failed (fused_check): the
@@ -118,12 +114,9 @@ int complete(glfsx_writer *w, WSlot &sl) {
   if (failed)
     if (int e = rehash_inflight(w)) return e;
   sl.busy = false;
-  for (uint64_t b = 0; b < sl.nblk; ++b) {
-    const uint8_t *ref = sl.h_refs.u8() + 64 * b;
-    if (int e = deliver(w->post, w->post_ctx, 0, ref, sl.h_ct.u8() + b * w->bs, w->bs)) return e;
-    if (int e = add_ref(w, 0, ref)) return e;
-    w->size += w->bs;
-  }
+  for (uint64_t b = 0; b < sl.nblk; ++b)
+    if (int e = replay_block(w, sl.h_refs.u8() + 64 * b, sl.h_ct.u8() + b * w->bs, w->bs))
+      return e;
   return 0;
 }
 
@@ -131,19 +124,20 @@ int complete(glfsx_writer *w, WSlot &sl) {
 // D2H of refs and ctext), finish the oldest batch still in flight if it
 // holds the next slot, and switch slots, carrying the partial block over.
 int submit(glfsx_writer *w) {
-  if (w->full == 0) return 0;
+  const uint64_t full = w->fill.full, partial = w->fill.partial;
+  if (full == 0) return 0;
   WSlot &sl = w->slot[w->cur];
   const int next = (w->cur + 1) % int(w->slot.size());
   WSlot &nx = w->slot[next];
   const WLane &L = w->lanes[sl.lane];
   DevScope dscope(L.dev);
-  const uint64_t nbytes = w->full * w->bs;
+  const uint64_t nbytes = full * w->bs;
   if (int e = sl.d_in.ensure(nbytes)) return e;
   if (int e = sl.d_ct.ensure(nbytes)) return e;
-  if (int e = sl.d_refs.ensure(w->full * 64)) return e;
+  if (int e = sl.d_refs.ensure(full * 64)) return e;
   if (w->post)
     if (int e = sl.h_ct.ensure(nbytes + 64)) return e;
-  if (int e = sl.h_refs.ensure(w->full * 64)) return e;
+  if (int e = sl.h_refs.ensure(full * 64)) return e;
   for (Event *ev : {&sl.up, &sl.hashed, &sl.done})
     if (int e = ev->ensure()) return e;
   if (!sl.on_dev)  // device-written bytes are already in d_in (s_up order)
@@ -155,31 +149,31 @@ int submit(glfsx_writer *w) {
   HIP_TRY(launch_post(sl.job, L.ws, fused_posts()));
   HIP_TRY(hipEventRecord(sl.hashed, L.ws));
   HIP_TRY(hipStreamWaitEvent(L.s_down, sl.hashed, 0));
-  HIP_TRY(hipMemcpyAsync(sl.h_refs.p, sl.d_refs.p, w->full * 64,
+  HIP_TRY(hipMemcpyAsync(sl.h_refs.p, sl.d_refs.p, full * 64,
                          hipMemcpyDeviceToHost, L.s_down));
   if (w->post)
     HIP_TRY(hipMemcpyAsync(sl.h_ct.p, sl.d_ct.p, nbytes, hipMemcpyDeviceToHost,
                            L.s_down));
   HIP_TRY(hipEventRecord(sl.done, L.s_down));
-  sl.nblk = w->full;
+  sl.nblk = full;
   sl.seq = ++w->seq;
   sl.busy = true;
   // `nx` is the oldest batch in flight (submitted nslots-1 batches ago):
   // completing it keeps Posts in order
   if (int e = complete(w, nx)) return e;
   if (sl.on_dev) {  // carry the partial block over on the device (one lane)
-    if (int e = nx.d_in.ensure(w->batch_blocks * w->bs + 64)) return e;
-    if (w->partial)
-      HIP_TRY(hipMemcpyAsync(nx.d_in.p, sl.d_in.u8() + nbytes, w->partial,
+    if (int e = nx.d_in.ensure(w->fill.cap() + 64)) return e;
+    if (partial)
+      HIP_TRY(hipMemcpyAsync(nx.d_in.p, sl.d_in.u8() + nbytes, partial,
                              hipMemcpyDeviceToDevice, L.s_up));
     nx.on_dev = true;
   } else {
-    if (int e = nx.h_in.grow(std::max<uint64_t>(w->partial, 1), 0)) return e;
-    if (w->partial) memcpy(nx.h_in.u8(), sl.h_in.u8() + nbytes, w->partial);
+    if (int e = nx.h_in.grow(std::max<uint64_t>(partial, 1), 0)) return e;
+    if (partial) memcpy(nx.h_in.u8(), sl.h_in.u8() + nbytes, partial);
     nx.on_dev = false;
   }
   w->cur = next;
-  w->full = 0;
+  w->fill.carry();
   return 0;
 }
 
@@ -187,8 +181,8 @@ int submit(glfsx_writer *w) {
 int slot_to_device(glfsx_writer *w) {
   WSlot &sl = w->slot[w->cur];
   if (sl.on_dev) return 0;
-  const uint64_t used = w->full * w->bs + w->partial;
-  if (int e = sl.d_in.ensure(w->batch_blocks * w->bs + 64)) return e;
+  const uint64_t used = w->fill.used();
+  if (int e = sl.d_in.ensure(w->fill.cap() + 64)) return e;
   if (used)
     HIP_TRY(hipMemcpyAsync(sl.d_in.p, sl.h_in.p, used, hipMemcpyHostToDevice, w->s_up));
   sl.on_dev = true;
@@ -198,7 +192,7 @@ int slot_to_device(glfsx_writer *w) {
 int slot_to_host(glfsx_writer *w) {
   WSlot &sl = w->slot[w->cur];
   if (!sl.on_dev) return 0;
-  const uint64_t used = w->full * w->bs + w->partial;
+  const uint64_t used = w->fill.used();
   if (int e = sl.h_in.grow(std::max<uint64_t>(used, 1), 0)) return e;
   if (used) {
     HIP_TRY(hipMemcpyAsync(sl.h_in.p, sl.d_in.p, used, hipMemcpyDeviceToHost, w->s_up));
@@ -214,38 +208,15 @@ int write_dev(glfsx_writer *w, const uint8_t *p, uint64_t n) {
   while (n) {
     if (int e = slot_to_device(w)) return e;
     WSlot &sl = w->slot[w->cur];
-    const uint64_t used = w->full * w->bs + w->partial;
-    const uint64_t cap = w->batch_blocks * w->bs;
-    const uint64_t take = std::min<uint64_t>(cap - used, n);
-    HIP_TRY(hipMemcpyAsync(sl.d_in.u8() + used, p, take, hipMemcpyDeviceToDevice, w->s_up));
+    const uint64_t take = std::min<uint64_t>(w->fill.room(), n);
+    HIP_TRY(hipMemcpyAsync(sl.d_in.u8() + w->fill.used(), p, take, hipMemcpyDeviceToDevice,
+                           w->s_up));
     p += take;
     n -= take;
-    w->full = (used + take) / w->bs;
-    w->partial = (used + take) % w->bs;
-    if (w->full == w->batch_blocks)
+    if (w->fill.add(take))
       if (int e = submit(w)) return e;
   }
   return 0;
-}
-
-// blob.go:184-206
-int finish_indexes(glfsx_writer *w, uint8_t out[64]) {
-  for (size_t i = 0; i < w->indexes.size(); ++i) {
-    if (i + 1 == w->indexes.size()) {
-      if (w->counts[i] == 0)
-        return post_one(w, 1, w->salts.index, nullptr, 0, out);
-      if (w->counts[i] == 1) {
-        memcpy(out, w->indexes[i].data(), 64);
-        return 0;
-      }
-    }
-    if (w->counts[i] > 0) {
-      uint8_t r[64];
-      if (int e = post_node(w, i, r)) return e;
-      if (int e = add_ref(w, i + 1, r)) return e;
-    }
-  }
-  return fail(GLFSX_E_ARG, "should not happen");
 }
 }  // namespace
 
@@ -272,8 +243,8 @@ glfsx_writer *glfsx_writer_new(uint64_t block_size, uint64_t store_max,
   }
   auto *w = new glfsx_writer();
   w->dev = c->dev;
-  w->bs = bs;
-  w->bf = bs / 64;  // blob.go:107
+  w->bs = w->fill.bs = w->index.node_len = bs;
+  w->index.bf = bs / 64;  // blob.go:107
   if (int e = derive_salts(c, salt, &w->salts)) {
     delete w;
     *err = e;
@@ -285,12 +256,10 @@ glfsx_writer *glfsx_writer_new(uint64_t block_size, uint64_t store_max,
   }
   w->post = post;
   w->post_ctx = post_ctx;
-  w->indexes.emplace_back();  // blob.go:111 (refs only, see post_node)
-  w->counts.push_back(0);
   uint64_t batch_mib = 64;
   if (const char *e = getenv("GLFSX_BATCH_MIB")) batch_mib = std::max(1ull, strtoull(e, nullptr, 10));
   if (const char *e = getenv("GLFSX_SLOTS")) w->nslots = std::min(kMaxSlots, std::max(2, atoi(e)));
-  w->batch_blocks = std::max<uint64_t>(1, (batch_mib << 20) / bs);
+  w->fill.batch_blocks = std::max<uint64_t>(1, (batch_mib << 20) / bs);
   w->slot.resize(w->nslots);
   for (WSlot &x : w->slot) take_slot(x, w->dev, 0);
   w->one = one_pool().take(w->dev);
@@ -311,7 +280,7 @@ glfsx_writer *glfsx_writer_new(uint64_t block_size, uint64_t store_max,
 int glfsx_writer_set_devices(glfsx_writer *w, const int *devs, int ndev) {
   if (!w) return fail(GLFSX_E_ARG, "null writer");
   if (!devs || ndev < 1 || ndev > 64) return fail(GLFSX_E_ARG, "need 1..64 devices");
-  if (w->seq || w->full || w->partial || w->size || w->sticky || w->ev_in)
+  if (w->seq || w->fill.used() || w->size || w->sticky || w->ev_in)
     return fail(GLFSX_E_ARG, "glfsx_writer_set_devices: the writer has already been written to");
   const int n = glfsx_device_count();
   for (int k = 0; k < ndev; ++k)
@@ -367,6 +336,10 @@ struct WriterCall {
     if (rc) w->err = last_error_text();
     return rc;
   }
+  // The writer is dead after its first error: that error again, or 0.
+  int dead() { return w->sticky ? done(fail(w->sticky, "%s", w->err.c_str())) : 0; }
+  // e is the writer's first error.
+  int stick(int e) { return done(w->sticky = e); }
 };
 
 // Drain: submit the staged complete blocks and deliver the Posts of every
@@ -398,14 +371,15 @@ constexpr uint64_t kFewBlocks = 8;
 int post_few(glfsx_writer *w, bool tail, bool *done) {
   *done = false;
   WSlot &sl = w->slot[w->cur];
-  if (sl.on_dev || w->full == 0 || w->full > kFewBlocks ||
+  FillCursor &f = w->fill;
+  if (sl.on_dev || f.full == 0 || f.full > kFewBlocks ||
       w->bs > kMaxMedLen || (w->bs & 15) || !sl.h_in.dp)
     return 0;
   if (int e = complete_all(w)) return e;
-  const uint64_t k = w->full + (tail && w->partial ? 1 : 0);
+  const uint64_t k = f.full + (tail && f.partial ? 1 : 0);
   OneBuf &o = w->one;
   if (w->post)
-    if (int e = o.h_ct.ensure(w->full * w->bs + w->partial + 64)) return e;
+    if (int e = o.h_ct.ensure(f.used() + 64)) return e;
   if (int e = o.h_ref.ensure(64 * k)) return e;
   std::vector<OneReq> reqs(k);
   std::vector<OneReq *> rp(k);
@@ -415,27 +389,23 @@ int post_few(glfsx_writer *w, bool tail, bool *done) {
     d.src = sl.h_in.dptr() + off;
     d.ctext = w->post ? o.h_ct.dptr() + off : nullptr;
     d.ref = o.h_ref.dptr() + 64 * b;
-    d.len = uint32_t(b < w->full ? w->bs : w->partial);
+    d.len = uint32_t(b < f.full ? w->bs : f.partial);
     d.present = d.len;
     set_keys(d, w->salts.raw, cidk(w));
     rp[b] = &reqs[b];
   }
   if (int e = one_post_many(w->dev, rp.data(), k)) return e;
-  // refs out first: an index node posted by add_ref reuses the single-post
+  // refs out first: an index node posted by addRef reuses the single-post
   // staging (its ctext lands on block 0's, already delivered)
   std::vector<uint8_t> refs(o.h_ref.u8(), o.h_ref.u8() + 64 * k);
-  for (uint64_t b = 0; b < k; ++b) {
-    const uint64_t len = reqs[b].d.len;
-    if (int e = deliver(w->post, w->post_ctx, 0, &refs[64 * b], o.h_ct.u8() + b * w->bs, len))
+  for (uint64_t b = 0; b < k; ++b)
+    if (int e = replay_block(w, &refs[64 * b], o.h_ct.u8() + b * w->bs, reqs[b].d.len))
       return e;
-    if (int e = add_ref(w, 0, &refs[64 * b])) return e;
-    w->size += len;
-  }
   if (tail)
-    w->partial = 0;
-  else if (w->partial)
-    memmove(sl.h_in.u8(), sl.h_in.u8() + w->full * w->bs, w->partial);
-  w->full = 0;
+    f.partial = 0;
+  else if (f.partial)
+    memmove(sl.h_in.u8(), sl.h_in.u8() + f.full * w->bs, f.partial);
+  f.carry();
   *done = true;
   return 0;
 }
@@ -454,59 +424,52 @@ int drain_strict(glfsx_writer *w) {
 int glfsx_writer_write(glfsx_writer *w, const void *data, size_t n) {
   if (!w) return fail(GLFSX_E_ARG, "null writer");
   WriterCall call(w);
-  if (w->sticky) return call.done(fail(w->sticky, "%s", w->err.c_str()));
+  if (int e = call.dead()) return e;
   if (n && !data) return call.done(fail(GLFSX_E_ARG, "null data"));
   const uint8_t *p = static_cast<const uint8_t *>(data);
   while (n) {
-    if (int e = slot_to_host(w)) return call.done(w->sticky = e);
+    if (int e = slot_to_host(w)) return call.stick(e);
     WSlot &sl = w->slot[w->cur];
-    const uint64_t used = w->full * w->bs + w->partial;
-    const uint64_t cap = w->batch_blocks * w->bs;  // slot holds up to a batch
-    const uint64_t take = std::min<uint64_t>(cap - used, n);
-    if (int e = sl.h_in.grow(used + take, used)) return call.done(w->sticky = e);
+    const uint64_t used = w->fill.used();
+    const uint64_t take = std::min<uint64_t>(w->fill.room(), n);
+    if (int e = sl.h_in.grow(used + take, used)) return call.stick(e);
     par_memcpy(sl.h_in.u8() + used, p, take, w->lanes[sl.lane].dev);
     p += take;
     n -= take;
-    w->full = (used + take) / w->bs;
-    w->partial = (used + take) % w->bs;
-    if (w->full == w->batch_blocks)
-      if (int e = submit(w)) return call.done(w->sticky = e);
+    if (w->fill.add(take))
+      if (int e = submit(w)) return call.stick(e);
   }
   if (w->strict)
-    if (int e = drain_strict(w)) return call.done(w->sticky = e);
+    if (int e = drain_strict(w)) return call.stick(e);
   return 0;
 }
 
 int glfsx_writer_reserve(glfsx_writer *w, void **buf, uint64_t *cap) {
   if (!w || !buf || !cap) return fail(GLFSX_E_ARG, "null argument");
   WriterCall call(w);
-  if (w->sticky) return call.done(fail(w->sticky, "%s", w->err.c_str()));
-  if (int e = slot_to_host(w)) return call.done(w->sticky = e);
+  if (int e = call.dead()) return e;
+  if (int e = slot_to_host(w)) return call.stick(e);
   WSlot &sl = w->slot[w->cur];
-  const uint64_t used = w->full * w->bs + w->partial;
-  const uint64_t room = w->batch_blocks * w->bs;
-  if (int e = sl.h_in.grow(room, used)) return call.done(w->sticky = e);
+  const uint64_t used = w->fill.used();
+  if (int e = sl.h_in.grow(w->fill.cap(), used)) return call.stick(e);
   *buf = sl.h_in.u8() + used;
-  *cap = room - used;  // >= 1: a full batch is submitted as soon as it fills
-  w->reserved = room - used;
+  *cap = w->fill.room();  // >= 1: a full batch is submitted as soon as it fills
+  w->reserved = w->fill.room();
   return 0;
 }
 
 int glfsx_writer_commit(glfsx_writer *w, uint64_t n) {
   if (!w) return fail(GLFSX_E_ARG, "null writer");
   WriterCall call(w);
-  if (w->sticky) return call.done(fail(w->sticky, "%s", w->err.c_str()));
+  if (int e = call.dead()) return e;
   if (n > w->reserved)
     return call.done(fail(GLFSX_E_ARG, "commit of %llu bytes, %llu reserved",
                           (unsigned long long)n, (unsigned long long)w->reserved));
   w->reserved = 0;
-  const uint64_t used = w->full * w->bs + w->partial + n;
-  w->full = used / w->bs;
-  w->partial = used % w->bs;
-  if (w->full == w->batch_blocks)
-    if (int e = submit(w)) return call.done(w->sticky = e);
+  if (w->fill.add(n))
+    if (int e = submit(w)) return call.stick(e);
   if (w->strict && n)
-    if (int e = drain_strict(w)) return call.done(w->sticky = e);
+    if (int e = drain_strict(w)) return call.stick(e);
   return 0;
 }
 
@@ -537,17 +500,16 @@ int glfsx_writer_read_at(glfsx_writer *w, glfsx_read_at_fn read_at, void *ctx,
   if (!w) return fail(GLFSX_E_ARG, "null writer");
   if (!read_at) return fail(GLFSX_E_ARG, "null reader");
   WriterCall call(w);
-  if (w->sticky) return call.done(fail(w->sticky, "%s", w->err.c_str()));
+  if (int e = call.dead()) return e;
   if (w->reserved) return call.done(fail(GLFSX_E_ARG, "staging lent out by glfsx_writer_reserve"));
   uint64_t total = 0;
   int rc = 0;
   while (total < n) {
-    if (int e = slot_to_host(w)) return call.done(w->sticky = e);
+    if (int e = slot_to_host(w)) return call.stick(e);
     WSlot &sl = w->slot[w->cur];  // free: submit completed it before moving on
-    const uint64_t used = w->full * w->bs + w->partial;
-    const uint64_t room = w->batch_blocks * w->bs;
-    if (int e = sl.h_in.grow(room, used)) return call.done(w->sticky = e);
-    const uint64_t want = std::min(room - used, n - total);
+    const uint64_t used = w->fill.used();
+    if (int e = sl.h_in.grow(w->fill.cap(), used)) return call.stick(e);
+    const uint64_t want = std::min(w->fill.room(), n - total);
     const int64_t r = par_read_at(read_at, ctx, sl.h_in.u8() + used, want, offset + total,
                                   read_threads(), w->lanes[sl.lane].dev);
     if (r < 0) {
@@ -556,15 +518,13 @@ int glfsx_writer_read_at(glfsx_writer *w, glfsx_read_at_fn read_at, void *ctx,
       break;
     }
     total += uint64_t(r);
-    w->full = (used + uint64_t(r)) / w->bs;
-    w->partial = (used + uint64_t(r)) % w->bs;
-    if (w->full == w->batch_blocks)
-      if (int e = submit(w)) return call.done(w->sticky = e);
+    if (w->fill.add(uint64_t(r)))
+      if (int e = submit(w)) return call.stick(e);
     if (uint64_t(r) < want) break;  // the end of the input
   }
   if (got) *got = total;
   if (w->strict && total)
-    if (int e = drain_strict(w)) return call.done(w->sticky = e);
+    if (int e = drain_strict(w)) return call.stick(e);
   return call.done(rc);
 }
 
@@ -590,8 +550,8 @@ int glfsx_writer_copy(glfsx_writer *w, const void *data, uint64_t n, uint64_t pi
 int glfsx_writer_flush(glfsx_writer *w) {
   if (!w) return fail(GLFSX_E_ARG, "null writer");
   WriterCall call(w);
-  if (w->sticky) return call.done(fail(w->sticky, "%s", w->err.c_str()));
-  if (int e = drain(w)) return call.done(w->sticky = e);
+  if (int e = call.dead()) return e;
+  if (int e = drain(w)) return call.stick(e);
   return 0;
 }
 
@@ -599,7 +559,7 @@ int glfsx_writer_write_device(glfsx_writer *w, const void *d_data, size_t n,
                               void *stream) {
   if (!w) return fail(GLFSX_E_ARG, "null writer");
   WriterCall call(w);
-  if (w->sticky) return call.done(fail(w->sticky, "%s", w->err.c_str()));
+  if (int e = call.dead()) return e;
   if (n && !d_data) return call.done(fail(GLFSX_E_ARG, "null data"));
   if (n == 0) return 0;
   if (w->lanes.size() != 1)
@@ -623,7 +583,7 @@ int glfsx_writer_write_device(glfsx_writer *w, const void *d_data, size_t n,
       if (int e = drain(w)) return e;
     return 0;
   };
-  if (int e = go()) return call.done(w->sticky = e);
+  if (int e = go()) return call.stick(e);
   return 0;
 }
 
@@ -632,7 +592,7 @@ int glfsx_writer_write_ctext_blocks(glfsx_writer *w, const void *const *blocks,
                                     const uint8_t *refs) {
   if (!w) return fail(GLFSX_E_ARG, "null writer");
   WriterCall call(w);
-  if (w->sticky) return call.done(fail(w->sticky, "%s", w->err.c_str()));
+  if (int e = call.dead()) return e;
   if (total == 0) return 0;
   if (!blocks || !refs) return call.done(fail(GLFSX_E_ARG, "null argument"));
   if (w->lanes.size() != 1)
@@ -734,7 +694,7 @@ int glfsx_writer_write_ctext_blocks(glfsx_writer *w, const void *const *blocks,
       if (int e = drain(w)) return e;
     return 0;
   };
-  if (int e = go()) return call.done(w->sticky = e);
+  if (int e = go()) return call.stick(e);
   return 0;
 }
 
@@ -767,23 +727,24 @@ const char *glfsx_writer_error(const glfsx_writer *w) {
 int glfsx_writer_finish(glfsx_writer *w, glfsx_root *out) {
   if (!w || !out) return fail(GLFSX_E_ARG, "null argument");
   WriterCall call(w);
-  if (w->sticky) return call.done(fail(w->sticky, "%s", w->err.c_str()));
+  if (int e = call.dead()) return e;
   bool few = false;
-  if (int e = post_few(w, true, &few)) return call.done(w->sticky = e);
+  if (int e = post_few(w, true, &few)) return call.stick(e);
   if (!few)
-    if (int e = drain(w)) return call.done(w->sticky = e);
-  if (w->partial) {  // blob.go:136-140: the tail block, never padded
+    if (int e = drain(w)) return call.stick(e);
+  if (const uint64_t tail = w->fill.partial) {  // blob.go:136-140: the tail block, never padded
     uint8_t ref[64];
     const WSlot &sl = w->slot[w->cur];
-    if (int e = post_one(w, 0, w->salts.raw, sl.on_dev ? sl.d_in.u8() : sl.h_in.u8(),
-                         w->partial, ref, sl.on_dev, &sl.h_in))
-      return call.done(w->sticky = e);
-    if (int e = add_ref(w, 0, ref)) return call.done(w->sticky = e);
-    w->size += w->partial;
-    w->partial = 0;
+    if (int e = post_one(w, 0, w->salts.raw, sl.on_dev ? sl.d_in.u8() : sl.h_in.u8(), tail,
+                         ref, sl.on_dev, &sl.h_in))  // (post_one delivers the Post)
+      return call.stick(e);
+    if (int e = account_block(w, ref, tail)) return call.stick(e);
+    w->fill.partial = 0;
   }
   uint8_t root[64];
-  if (int e = finish_indexes(w, root)) return call.done(w->sticky = e);
+  int e = w->index.finish(root, node_poster(w));
+  if (e == IndexStack::kShouldNotHappen) e = fail(GLFSX_E_ARG, "should not happen");
+  if (e) return call.stick(e);
   memcpy(out->ref, root, 64);
   out->size = w->size;
   out->block_size = w->bs;

@@ -2,6 +2,7 @@
 // (writer.cpp).
 #pragma once
 #include "host.h"
+#include "writer_book.h"
 
 namespace glfsx {
 namespace host __attribute__((visibility("hidden"))) {  // (per namespace body)
@@ -161,14 +162,14 @@ struct glfsx_writer {
   // batch k+1's H2D overlaps batch k's D2H on the full-duplex link
   glfsx::host::Streams home;
   hipStream_t ws = nullptr, s_up = nullptr, s_down = nullptr;  // home's
-  uint64_t bs = 0, bf = 0;
+  uint64_t bs = 0;
   glfsx::host::Salts salts{};
   uint8_t cid_key[32]{};
   bool has_cid_key = false;
   glfsx_post_fn post = nullptr;
   void *post_ctx = nullptr;
-  std::vector<std::vector<uint8_t>> indexes;  // index.go Index per level
-  std::vector<uint64_t> counts;
+  glfsx::IndexStack index;    // the index levels and their Post order (writer_book.h)
+  std::vector<uint8_t> node;  // an index node above kMaxMedLen, zero padded
   uint64_t size = 0;
   glfsx::host::OneBuf one;             // single posts (index nodes, the tail block)
   // device input (write_device / write_ctext): events ordering the caller's
@@ -180,9 +181,7 @@ struct glfsx_writer {
   int nslots = 3;            // slots per lane
   int cur = 0;               // slot being filled
   uint64_t seq = 0;
-  uint64_t batch_blocks = 1;
-  uint64_t full = 0;         // complete blocks staged in slot[cur]
-  uint64_t partial = 0;      // bytes of the block being filled
+  glfsx::FillCursor fill;    // where the next byte goes in slot[cur] (writer_book.h)
   uint64_t reserved = 0;     // bytes lent out by glfsx_writer_reserve
   bool strict = false;       // deliver every completed block's Post before
                              // Write returns (blob.go:120-133 error timing)

@@ -2,6 +2,7 @@
 // job builders, stand-alone.  Built by tests/test_host_units.py with the host
 // compiler under -fsanitize=address,undefined; no GPU call is made (nothing
 // here instantiates a buffer or touches a stream).
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 
@@ -166,9 +167,113 @@ static void test_jobs() {
   }
 }
 
+template <size_t N>
+static bool all_zero(const uint32_t (&w)[N]) {
+  for (uint32_t x : w)
+    if (x) return false;
+  return true;
+}
+
+// The builders of the batch jobs: every field set, every other field zero.
+static void test_batch_jobs() {
+  static uint8_t src[1], ct[1], refs[1];
+  static uint64_t offs[1], lens[1];
+  static uint32_t status[1];
+  const SmallJob s = small_job(src, ct, offs, lens, 7, 900, 512, refs);
+  CHECK(s.src == src && s.ctext == ct && s.offs == offs && s.lens == lens && s.refs == refs);
+  CHECK(s.n == 7 && s.max_len == 900 && s.small_max == 512);
+  CHECK(all_zero(s.raw_salt) && all_zero(s.index_salt) && all_zero(s.cid_key) && !s.cid_keyed);
+  CHECK(!s.hex_out && !s.hex_pos && !s.cid_wait && s.passes == 0);
+  CHECK(small_job(src, nullptr, offs, lens, 1, 0, 0, refs).ctext == nullptr);
+  const RaggedJob r = ragged_job(src, ct, offs, lens, 9, kRaggedAll, 1 << 20, refs);
+  CHECK(r.src == src && r.ctext == ct && r.offs == offs && r.lens == lens && r.refs == refs);
+  CHECK(r.n == 9 && r.lo == kRaggedAll && r.hi == 1 << 20);
+  CHECK(all_zero(r.salt) && all_zero(r.cid_key) && !r.cid_keyed);
+  for (uint64_t bs : {uint64_t(64), uint64_t(4096), uint64_t(1) << 20}) {
+    for (uint64_t total : {uint64_t(0), uint64_t(1), bs - 1, bs, bs + 1, 3 * bs, 3 * bs + 5}) {
+      const OpenJob o = open_job(ct, src, total, bs, refs, status);
+      CHECK(o.ctext == ct && o.ptext == src && o.refs == refs && o.status == status);
+      CHECK(o.bs == bs && o.n == (total ? total / bs + (total % bs ? 1 : 0) : 1));
+      CHECK(o.last_len == total - (o.n - 1) * bs && o.last_len <= bs);
+      CHECK(all_zero(o.salt) && all_zero(o.cid_key) && !o.salted && !o.cid_keyed);
+    }
+  }
+  CHECK(open_job(ct, nullptr, 64, 64, refs, status).ptext == nullptr);
+  const OpenRaggedJob g = open_ragged_job(ct, src, offs, lens, 5, 777, refs, status);
+  CHECK(g.ctext == ct && g.ptext == src && g.offs == offs && g.lens == lens);
+  CHECK(g.n == 5 && g.max_len == 777 && g.refs == refs && g.status == status);
+  CHECK(all_zero(g.salt) && all_zero(g.cid_key) && !g.salted && !g.cid_keyed);
+  static uint64_t name_offs[1], type_offs[1], sizes[1], block_sizes[1], scratch[8];
+  static uint32_t modes[1];
+  const TreeJob t = tree_job(3, src, name_offs, modes, ct, type_offs, refs, sizes, block_sizes,
+                             scratch, 8, ct, 55);
+  CHECK(t.n == 3 && t.names == src && t.name_offs == name_offs && t.modes == modes);
+  CHECK(t.types == ct && t.type_offs == type_offs && t.roots == refs && t.sizes == sizes);
+  CHECK(t.block_sizes == block_sizes && t.scratch == scratch && t.total == scratch + 7);
+  CHECK(t.out == ct && t.cap == 55);
+  CHECK(!t.line_ends && !t.hex_pos && t.prio == 0 && !t.prefix_host);
+  // the read side's keys, with and without a salt and a CID key
+  uint8_t salt[32], key[32];
+  uint32_t salt_w[8], key_w[8], iv[8];
+  for (int i = 0; i < 32; ++i) {
+    salt[i] = uint8_t(0x40 + i);
+    key[i] = uint8_t(5 * i + 2);
+  }
+  words_from_key(salt_w, salt);
+  words_from_key(key_w, key);
+  blake3_iv_words(iv);
+  for (const uint8_t *sa : {static_cast<const uint8_t *>(nullptr), static_cast<const uint8_t *>(salt)})
+    for (const uint8_t *cid : {static_cast<const uint8_t *>(nullptr),
+                               static_cast<const uint8_t *>(key)}) {
+      OpenJob o = open_job(ct, src, 100, 64, refs, status);
+      OpenRaggedJob q = open_ragged_job(ct, src, offs, lens, 5, 777, refs, status);
+      o.salted = q.salted = !sa;  // whatever was there is overwritten
+      o.cid_keyed = q.cid_keyed = !cid;
+      open_keys(o, sa, cid);
+      open_keys(q, sa, cid);
+      CHECK(o.salted == (sa != nullptr) && q.salted == (sa != nullptr));
+      CHECK(o.cid_keyed == (cid != nullptr) && q.cid_keyed == (cid != nullptr));
+      CHECK(memcmp(o.cid_key, cid ? key_w : iv, 32) == 0);
+      CHECK(memcmp(q.cid_key, cid ? key_w : iv, 32) == 0);
+      if (sa) CHECK(memcmp(o.salt, salt_w, 32) == 0 && memcmp(q.salt, salt_w, 32) == 0);
+      else CHECK(all_zero(o.salt) && all_zero(q.salt));  // not read when unsalted
+      CHECK(o.n == 2 && o.last_len == 36 && q.n == 5 && q.max_len == 777);  // the rest stays
+    }
+}
+
+// The GLFSX_E_CORRUPT texts (fail() is runtime.cpp's: this one keeps the text).
+static std::string g_text;
+namespace glfsx {
+namespace host {
+int fail(int code, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_text = buf;
+  return code;
+}
+}  // namespace host
+}  // namespace glfsx
+
+static void test_corrupt_texts() {
+  CHECK(std::string(failed_checks(1)) == "failed its CID check");
+  CHECK(std::string(failed_checks(2)) == "failed its DEK check");
+  CHECK(std::string(failed_checks(3)) == "failed its CID and DEK checks");
+  CHECK(corrupt_fail("block", 4, 70, 3, 2) == GLFSX_E_CORRUPT);
+  CHECK(g_text == "block 4 of 70 failed its CID and DEK checks (2 bad in all)");
+  CHECK(corrupt_fail("message", 0, 1, 1, 1) == GLFSX_E_CORRUPT);
+  CHECK(g_text == "message 0 of 1 failed its CID check (1 bad in all)");
+  CHECK(corrupt_fail("block", 18446744073709551615ull, 9, 2, 3) == GLFSX_E_CORRUPT);
+  CHECK(g_text == "block 18446744073709551615 of 9 failed its DEK check (3 bad in all)");
+}
+
 int main() {
   test_pool();
   test_jobs();
+  test_batch_jobs();
+  test_corrupt_texts();
   if (g_failed) {
     fprintf(stderr, "host_units_test: %d checks failed\n", g_failed);
     return 1;

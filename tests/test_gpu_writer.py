@@ -376,6 +376,79 @@ def test_read_from_store_error(gpu, O):
     assert [(k, r) for k, r, _ in st.inner.log] == want_posts
 
 
+@pytest.mark.parametrize("strict", [False, True])
+def test_all_five_feeders_in_one_writer(gpu, O, strict, tmp_path):
+    """One Writer fed by write, reserve / commit, read_at (a callback that
+    returns short reads), read_fd and write_device in seeded random pieces, at
+    block size 192 (bf 3, not a divisor of the batch) with 1 MiB batches over
+    3 MiB + 77 B: several batch boundaries with a carried partial block,
+    staging moves between host and device, and a deep index.  Root and the
+    whole Post log (kind, ref, ctext) == the oracle's Create."""
+    import os
+    import torch
+    from glfs_amd import bigblob
+    N = gpu
+    bs, size = 192, (3 << 20) + 77
+    data = O.fill_splitmix(size, 57)
+    want_root, _, _, want = O.create(data, bs)
+    path = tmp_path / "feed.bin"
+    path.write_bytes(data)
+    d_data = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()
+    mv = memoryview(data)
+
+    def short_read_at(buf, off):
+        k = max(0, min(len(buf), 10_007, size - off))
+        buf[:k] = mv[off:off + k]
+        return k
+
+    old = os.environ.get("GLFSX_BATCH_MIB")
+    os.environ["GLFSX_BATCH_MIB"] = "1"
+    try:
+        st = bigblob.MemStore(bs)
+        w = bigblob.Machine(bs).new_writer(st, None, strict=strict)
+    finally:
+        if old is None:
+            del os.environ["GLFSX_BATCH_MIB"]
+        else:
+            os.environ["GLFSX_BATCH_MIB"] = old
+    fd = os.open(path, os.O_RDONLY)
+    rng = random.Random(9)
+    used = set()
+    try:
+        off = 0
+        while off < size:
+            p = min(size - off, rng.choice([1, bs - 1, bs, bs + 1, rng.randrange(1, 9 * bs),
+                                            rng.randrange(1, 300_000)]))
+            feeder = rng.choice(["write", "reserve", "read_at", "read_fd", "device"])
+            used.add(feeder)
+            if feeder == "write":
+                w.write(data[off:off + p])
+            elif feeder == "reserve":
+                buf, cap = ctypes.c_void_p(), ctypes.c_uint64()
+                N.check(N.lib.glfsx_writer_reserve(w._w, ctypes.byref(buf), ctypes.byref(cap)))
+                assert cap.value >= 1
+                p = min(p, cap.value)
+                ctypes.memmove(buf.value, data[off:off + p], p)
+                rc = N.lib.glfsx_writer_commit(w._w, p)
+                N.check(rc, (N.lib.glfsx_writer_error(w._w) or b"").decode())
+            elif feeder == "read_at":
+                assert w.read_at(short_read_at, off, p) == p
+            elif feeder == "read_fd":
+                assert w.read_fd(fd, off, p) == p
+            else:
+                w.write_device(d_data.data_ptr() + off, p, None)
+            off += p
+        root = w.finish()
+    finally:
+        w.close()
+        os.close(fd)
+    assert used == {"write", "reserve", "read_at", "read_fd", "device"}
+    assert root.ref.marshal_binary() == want_root and root.size == size
+    assert [(k, r) for k, r, _ in st.log] == [(k, r) for k, r, _, _ in want]
+    assert all(st.blobs[r[:32]] == ct for _, r, _, ct in want)
+
+
 def test_commit_more_than_reserved_fails(gpu):
     N = gpu
     err = ctypes.c_int()

@@ -2,38 +2,23 @@
 inverse of glfsx_tree_encode; grammar in glfs_amd/csrc/tree_line.h) and
 tree.read_tree_bytes over it.  CPU-only."""
 import ctypes
-import os
 import random
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import tree_decode_corpus as C
+from cunit import build_and_run
 from glfs_amd import _native as N, tree as T
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_decoder_under_sanitizers(tmp_path):
     """tests/c/tree_decode_test.cpp (its own main, tree.cpp compiled in) with
     -fsanitize=address,undefined: both round trips and the negative corpus,
     each input decoded from a heap buffer of exactly its length."""
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    out = str(tmp_path / "tree_decode_test")
-    subprocess.check_call(
-        [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-pthread", "-fsanitize=address,undefined",
-         "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "glfs_amd", "csrc"),
-         os.path.join(ROOT, "tests", "c", "tree_decode_test.cpp"), "-o", out])
     corpus = str(tmp_path / "negative.bin")
     assert C.write_negative_corpus(corpus) > 1000
-    p = subprocess.run([out, corpus], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "tree_decode_test: ok" in p.stdout
-    assert p.stderr == "", p.stderr  # the sanitizers report nothing
+    build_and_run(tmp_path, "tree_decode_test", args=[corpus], timeout=300)
 
 
 @pytest.fixture(scope="module")
