@@ -29,6 +29,10 @@ GLFSX_BAD_DEK = 2
 GLFSX_TREE_NONCANON = 1
 GLFSX_TREE_ORDER = 2
 GLFSX_TREE_NAME = 4
+GLFSX_JOIN_ONLY = 0
+GLFSX_JOIN_TREES = 1
+GLFSX_JOIN_SAME = 2
+GLFSX_JOIN_DIFF = 3
 GLFSX_STORE_TRUST = 0
 GLFSX_STORE_HASH = 1
 
@@ -54,6 +58,13 @@ class DeviceError(GlfsxError):
 class glfsx_root(ctypes.Structure):
     _fields_ = [("ref", ctypes.c_uint8 * 64), ("size", ctypes.c_uint64),
                 ("block_size", ctypes.c_uint64)]
+
+
+class glfsx_tree_cols(ctypes.Structure):
+    """One side of a join or a select: the decoder's columns as addresses."""
+    _fields_ = [("n", ctypes.c_uint64)] + [(k, ctypes.c_void_p) for k in (
+        "names", "name_offs", "modes", "types", "type_offs", "roots", "sizes", "block_sizes",
+        "status")]
 
 
 POST_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
@@ -147,6 +158,14 @@ SIGNATURES = {
     "glfsx_tree_decode_device": (_INT, [_VP, _U64, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _VP,
                                         _VP, _VP, _VP, _U64, ctypes.POINTER(ctypes.c_uint64),
                                         _VP]),
+    "glfsx_tree_join": (_INT, [ctypes.POINTER(glfsx_tree_cols), ctypes.POINTER(glfsx_tree_cols),
+                               _VP, _VP, _VP]),
+    "glfsx_tree_join_device": (_INT, [ctypes.POINTER(glfsx_tree_cols),
+                                      ctypes.POINTER(glfsx_tree_cols), _VP, _VP, _VP, _VP]),
+    "glfsx_tree_select_device": (_INT, [ctypes.POINTER(glfsx_tree_cols),
+                                        ctypes.POINTER(glfsx_tree_cols), _VP, _U64, _VP, _U64,
+                                        _VP, _VP, _VP, _U64, _VP, _VP, _VP, _VP, _VP, _U64,
+                                        ctypes.POINTER(ctypes.c_uint64), _VP]),
     "glfsx_fill_splitmix_blobs_device": (_INT, [_VP, _U64, _U64, _U64, _VP]),
     "glfsx_post_tree_device": (_INT, [_U64, _U64, _CP, _CP, _CP, _VP, _VP, _VP, _U64, _VP,
                                       _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U64, _VP, _U64,

@@ -547,3 +547,96 @@ int glfsx_tree_decode_device(const void *d_data, uint64_t len, uint8_t *d_names,
   return 0;
 }
 
+namespace {
+// One side as the kernels take it; what must be there for n entries: the
+// names always, the ref columns with `refs`, the modes with `modes`.
+int tree_cols(const glfsx_tree_cols *c, bool refs, bool modes, TreeCols *out) {
+  if (!c) return fail(GLFSX_E_ARG, "null column set");
+  if (c->n && (!c->name_offs ||
+               (refs && (!c->type_offs || !c->roots || !c->sizes || !c->block_sizes)) ||
+               (modes && !c->modes)))
+    return fail(GLFSX_E_ARG, "null column");
+  *out = TreeCols{c->n,     c->names, c->name_offs,   c->modes, c->types, c->type_offs,
+                  c->roots, c->sizes, c->block_sizes, c->status};
+  return 0;
+}
+}  // namespace
+
+int glfsx_tree_join_device(const glfsx_tree_cols *a, const glfsx_tree_cols *b,
+                           int64_t *d_a_match, int64_t *d_b_match, uint8_t *d_a_class,
+                           void *stream) {
+  Ctx *c;
+  if (int e = ctx_get(&c)) return e;  // before any argument is looked at
+  TreeJoinJob j{};
+  if (int e = tree_cols(a, d_a_class != nullptr, false, &j.a)) return e;
+  if (int e = tree_cols(b, d_a_class != nullptr, false, &j.b)) return e;
+  if ((j.a.n + j.b.n + kTreeWG - 1) / kTreeWG > 0x7FFFFFFFull)
+    return fail(GLFSX_E_UNSUPPORTED, "entries above the kernel's grid limit");
+  j.a_match = d_a_match;
+  j.b_match = d_b_match;
+  j.a_class = d_a_class;
+  HIP_TRY(launch_tree_join(j, pick_stream(c, stream)));
+  return 0;
+}
+
+int glfsx_tree_select_device(const glfsx_tree_cols *a, const glfsx_tree_cols *b,
+                             const int64_t *d_sel, uint64_t k, uint8_t *d_names,
+                             uint64_t names_cap, uint64_t *d_name_offs, uint32_t *d_modes,
+                             uint8_t *d_types, uint64_t types_cap, uint64_t *d_type_offs,
+                             uint8_t *d_roots, uint64_t *d_sizes, uint64_t *d_block_sizes,
+                             uint32_t *d_status, uint64_t k_cap, uint64_t counts[2],
+                             void *stream) {
+  Ctx *c;
+  if (int e = ctx_get(&c)) return e;  // before any argument is looked at
+  if (!counts || (k && !d_sel)) return fail(GLFSX_E_ARG, "null argument");
+  counts[0] = counts[1] = 0;
+  TreeSelectJob j{};
+  if (int e = tree_cols(a, true, d_modes != nullptr, &j.a)) return e;
+  if (int e = tree_cols(b, true, d_modes != nullptr, &j.b)) return e;
+  if ((k + kTreeWG - 1) / kTreeWG > 0x7FFFFFFFull)
+    return fail(GLFSX_E_UNSUPPORTED, "k above the kernels' grid limit");
+  hipStream_t s = pick_stream(c, stream);
+  if (k == 0) {  // no entries: the two offset arrays hold their one word
+    if (d_name_offs) HIP_TRY(hipMemsetAsync(d_name_offs, 0, 8, s));
+    if (d_type_offs) HIP_TRY(hipMemsetAsync(d_type_offs, 0, 8, s));
+    HIP_TRY(stream_wait(s));
+    return 0;
+  }
+  const bool per_entry = d_name_offs || d_modes || d_type_offs || d_roots || d_sizes ||
+                         d_block_sizes || d_status;
+  if (int e = c->d_tree.ensure(8 * tree_select_words(k))) return e;
+  if (int e = c->h_small.ensure(64)) return e;
+  j.sel = d_sel;
+  j.k = k;
+  j.scratch = reinterpret_cast<uint64_t *>(c->d_tree.p);
+  j.write = (per_entry || d_names || d_types) && !(per_entry && k > k_cap);
+  j.names = d_names;
+  j.names_cap = names_cap;
+  j.name_offs = d_name_offs;
+  j.modes = d_modes;
+  j.types = d_types;
+  j.types_cap = types_cap;
+  j.type_offs = d_type_offs;
+  j.roots = d_roots;
+  j.sizes = d_sizes;
+  j.block_sizes = d_block_sizes;
+  j.status = d_status;
+  HIP_TRY(hipMemsetAsync(j.scratch, 0, 24, s));  // the two totals and the bad-sel flag
+  HIP_TRY(launch_tree_select(j, s));
+  HIP_TRY(hipMemcpyAsync(c->h_small.p, j.scratch, 24, hipMemcpyDeviceToHost, s));
+  HIP_TRY(stream_wait(s));
+  uint64_t res[3];
+  memcpy(res, c->h_small.p, 24);
+  counts[0] = res[0];
+  counts[1] = res[1];
+  if (res[2]) return fail(GLFSX_E_ARG, "a sel value names no entry of either side");
+  if (per_entry && k > k_cap)
+    return fail(GLFSX_E_ARG, "%llu entries selected, k_cap holds %llu", (unsigned long long)k,
+                (unsigned long long)k_cap);
+  if ((d_names && res[0] > names_cap) || (d_types && res[1] > types_cap))
+    return fail(GLFSX_E_ARG, "selected names / types need %llu / %llu bytes, buffers hold %llu / %llu",
+                (unsigned long long)res[0], (unsigned long long)res[1],
+                (unsigned long long)names_cap, (unsigned long long)types_cap);
+  return 0;
+}
+

@@ -347,6 +347,57 @@ inline uint64_t tree_decode_words(const uint8_t *data, uint64_t len, uint64_t n_
 }
 hipError_t launch_tree_decode(const TreeDecodeJob &j, hipStream_t s);
 
+// Tree against tree (tree_join_kernels.h): see glfsx_tree_join_device and
+// glfsx_tree_select_device.  One side's columns, device pointers (the layout
+// of glfsx_tree_cols).
+struct TreeCols {
+  uint64_t n;
+  const uint8_t *names;
+  const uint64_t *name_offs;  // n + 1
+  const uint32_t *modes;
+  const uint8_t *types;
+  const uint64_t *type_offs;  // n + 1
+  const uint8_t *roots;       // 64 B per entry
+  const uint64_t *sizes, *block_sizes;
+  const uint32_t *status;     // nullable: zeros
+};
+// One launch: lane g < a.n looks a's entry g up in b, lane a.n + g b's entry
+// g in a (tree_join.h).  Outputs nullable.
+struct TreeJoinJob {
+  TreeCols a, b;
+  int64_t *a_match, *b_match;
+  uint8_t *a_class;
+};
+hipError_t launch_tree_join(const TreeJoinJob &j, hipStream_t s);
+// Four launches whatever k (k > 0): the selected strings' lengths scanned
+// within each workgroup, k_tree_prefix over the workgroups' name and type
+// totals, the write.  scratch: tree_select_words(k) words, the first three
+// zero before the launches; after them they hold the bytes of the names, of
+// the types, and 1 if a sel value named no entry.  The write kernel is
+// launched only with write set, and writes nothing when that flag is set or
+// a total exceeds its capacity.
+struct TreeSelectJob {
+  TreeCols a, b;
+  const int64_t *sel;
+  uint64_t k;
+  uint64_t *scratch;
+  bool write;
+  uint8_t *names;             // every output nullable
+  uint64_t names_cap;
+  uint64_t *name_offs;        // k + 1
+  uint32_t *modes;
+  uint8_t *types;
+  uint64_t types_cap;
+  uint64_t *type_offs;        // k + 1
+  uint8_t *roots;
+  uint64_t *sizes, *block_sizes;
+  uint32_t *status;
+};
+inline uint64_t tree_select_words(uint64_t k) {
+  return 8 + 2 * ((k + kTreeWG - 1) / kTreeWG) + 2 * k;
+}
+hipError_t launch_tree_select(const TreeSelectJob &j, hipStream_t s);
+
 // n blobs of len bytes (len % 8 == 0), blob b = the splitmix stream of seed
 // seed0 + b (see oracle_fill_splitmix_blobs).
 hipError_t launch_fill_blobs(uint8_t *dst, uint64_t n, uint64_t len, uint64_t seed0,

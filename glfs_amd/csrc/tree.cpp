@@ -1,6 +1,7 @@
 // tree.cpp -- host encoder of glfs tree blobs (tree.go:284-320 TreeWriter)
 // and its inverse, the decoder of canonical lines (glfsx_tree_decode; the
-// grammar is tree_line.h's, shared with the kernels).
+// grammar is tree_line.h's, shared with the kernels), and the join of two
+// trees' entries by name (glfsx_tree_join; tree_join.h's functions).
 //
 // A tree blob is JSON lines, one TreeEntry per Put (tree.go:300-316), written
 // by Go's json.Encoder: struct fields in declaration order with their tags
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "../../include/glfsx.h"
+#include "tree_join.h"
 #include "tree_line.h"
 
 namespace {
@@ -351,5 +353,47 @@ extern "C" int glfsx_tree_decode(const uint8_t *data, uint64_t len, uint8_t *nam
       }
     }
   });
+  return GLFSX_OK;
+}
+
+// ------------------------------------------------------------------- join
+// compareTrees' matching (compare.go:52-124): every entry of one side looked
+// up in the other (tree_join.h, shared with the kernel), by ranges of entries.
+static_assert(GLFSX_JOIN_ONLY == glfsx::kJoinOnly && GLFSX_JOIN_TREES == glfsx::kJoinTrees &&
+                  GLFSX_JOIN_SAME == glfsx::kJoinSame && GLFSX_JOIN_DIFF == glfsx::kJoinDiff,
+              "tree_join.h and glfsx.h name the same classes");
+
+extern "C" int glfsx_tree_join(const glfsx_tree_cols *a, const glfsx_tree_cols *b,
+                               int64_t *a_match, int64_t *b_match, uint8_t *a_class) {
+  using namespace glfsx;
+  if (!a || !b) return GLFSX_E_ARG;
+  auto names_ok = [](const glfsx_tree_cols *c) { return c->n == 0 || c->name_offs; };
+  if (!names_ok(a) || !names_ok(b)) return GLFSX_E_ARG;
+  auto refs_ok = [](const glfsx_tree_cols *c) {
+    return c->n == 0 || (c->type_offs && c->roots && c->sizes && c->block_sizes);
+  };
+  if (a_class && (!refs_ok(a) || !refs_ok(b))) return GLFSX_E_ARG;
+  auto side = [](const glfsx_tree_cols *x, const glfsx_tree_cols *y, int64_t *match, uint8_t *cls) {
+    if (!match && !cls) return;
+    parallel_ranges(x->n, [&](uint64_t, uint64_t lo, uint64_t hi) {
+      for (uint64_t i = lo; i < hi; ++i) {
+        const uint64_t at = x->name_offs[i];
+        const int64_t j = tj_find(y->names, y->name_offs, y->n, x->names + at,
+                                  x->name_offs[i + 1] - at);
+        if (match) match[i] = j;
+        if (!cls) continue;
+        if (j < 0) {
+          cls[i] = kJoinOnly;
+          continue;
+        }
+        const uint64_t ta = x->type_offs[i], tb = y->type_offs[j];
+        cls[i] = tj_class(x->types + ta, x->type_offs[i + 1] - ta, x->roots + 64 * i, x->sizes[i],
+                          x->block_sizes[i], y->types + tb, y->type_offs[j + 1] - tb,
+                          y->roots + 64 * j, y->sizes[j], y->block_sizes[j]);
+      }
+    });
+  };
+  side(a, b, a_match, a_class);
+  side(b, a, b_match, nullptr);
   return GLFSX_OK;
 }

@@ -20,12 +20,14 @@
 // workgroup's span, which it shares with its neighbours, are stored one by
 // one).  A workgroup whose lines do not fit the LDS image stores bytes.
 //
-// The read side of the same bytes is tree_decode_kernels.h, included below.
+// The read side of the same bytes is tree_decode_kernels.h, and the join and
+// select of two trees' decoded columns tree_join_kernels.h, both included below.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device_common.h"
 #include "kernels.h"
+#include "tree_join.h"
 #include "tree_line.h"
 
 namespace glfsx {
@@ -535,5 +537,9 @@ hipError_t launch_fill_blobs(uint8_t *dst, uint64_t n, uint64_t len, uint64_t se
 // the decoder of the same lines: k_td_count / k_td_index / k_td_parse /
 // k_td_write and launch_tree_decode
 #include "tree_decode_kernels.h"
+
+// tree against tree over those columns: k_tree_join, k_ts_len / k_ts_write
+// and launch_tree_join / launch_tree_select
+#include "tree_join_kernels.h"
 
 }  // namespace glfsx

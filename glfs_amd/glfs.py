@@ -34,6 +34,16 @@ class Ref:
         return d
 
 
+@dataclass(frozen=True)
+class Diff:
+    """compare.go:9-17 Diff{Left, Right, Both}, the result of Compare: what
+    only left holds, what only right holds, what both hold; each a Ref or
+    None."""
+    left: Optional[Ref]
+    right: Optional[Ref]
+    both: Optional[Ref]
+
+
 class ErrRefType(TypeError):
     """errors.go:20-26."""
 
@@ -318,6 +328,19 @@ class Machine:
         """tree.go:137-143."""
         from .tree import get_tree_slice
         return get_tree_slice(store, ref, max_ents, **{**self._read_kw(TYPE_TREE), **kw})
+
+    # A pair of trees with at least this many entries between them is
+    # compared on the GPU (compare.py's column route); the measured crossover
+    # (DESIGN 4, "Tree against tree").
+    COMPARE_DEVICE_MIN = 512
+
+    def compare(self, dst, src, left: Ref, right: Ref, **kw) -> "Diff":
+        """compare.go:19-50 Compare: Diff(left, right, both), each a Ref or
+        None.  New trees are posted to dst; left and right are read from src
+        (with the verified read on a Machine made with_verify).  Trees keep
+        their first 10^6 entries (compare.go:31,35)."""
+        from .compare import compare
+        return compare(self, dst, src, left, right, **kw)
 
 
 _default: Optional[Machine] = None

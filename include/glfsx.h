@@ -37,6 +37,9 @@
  *   glfsx_tree_encode      tree.go:300-316 TreeWriter.Put's JSON lines, batched
  *   glfsx_tree_decode      tree.go:340-372 TreeReader.Next's decoding of those
  *                          lines, batched; canonical lines only, others reported
+ *   glfsx_tree_join*,      compare.go:52-124 compareTrees' onlyInFirst /
+ *   glfsx_tree_select_device forEachInBoth (a tree.go:22-30 Lookup per entry) and
+ *                          the assembly of its three result trees, on columns
  *   glfsx_store_*          the store under ref.go:103 (bcsdk.WO / MemStore [ext])
  *                          with a pre-hashed Post that takes the GPU CID
  *   glfsx_chacha20_xor*    bigblob/ref.go:137-144  cryptoXOR (read side decrypt)
@@ -523,6 +526,75 @@ int glfsx_tree_decode_device(const void *d_data, uint64_t len, uint8_t *d_names,
                              uint64_t *d_type_offs, uint8_t *d_roots, uint64_t *d_sizes,
                              uint64_t *d_block_sizes, uint32_t *d_status, uint64_t n_cap,
                              uint64_t counts[5], void *stream);
+
+/* --- tree against tree (compare.go:52-124, tree.go:22-30) --------------- */
+/* One side of a join or a select: n entries as the columns glfsx_tree_decode
+ * gives (name_offs / type_offs: n + 1 words; roots: 64 n bytes).  modes and
+ * status are read by glfsx_tree_select_device only; a NULL status reads as
+ * zeros.  With n == 0 every pointer may be NULL. */
+typedef struct glfsx_tree_cols {
+  uint64_t n;
+  const uint8_t *names;
+  const uint64_t *name_offs;
+  const uint32_t *modes;
+  const uint8_t *types;
+  const uint64_t *type_offs;
+  const uint8_t *roots;
+  const uint64_t *sizes;
+  const uint64_t *block_sizes;
+  const uint32_t *status;
+} glfsx_tree_cols;
+
+/* a_class of glfsx_tree_join */
+#define GLFSX_JOIN_ONLY 0u  /* no entry of that name on the other side */
+#define GLFSX_JOIN_TREES 1u /* both types are exactly "tree" */
+#define GLFSX_JOIN_SAME 2u  /* equal types (not "tree"), CID, DEK, size, block size */
+#define GLFSX_JOIN_DIFF 3u  /* every other match, differing types included */
+
+/* compareTrees' matching of two trees' entries by name (compare.go:52-124:
+ * onlyInFirst and forEachInBoth, each a Lookup per entry, tree.go:22-30) for
+ * all entries at once, on host cores.  Names compare as strings.Compare does:
+ * unsigned bytes, a proper prefix first.  a_match[i] (a->n words) is the
+ * index in b of the entry named as a's entry i, or -1; b_match (b->n words)
+ * the same seen from b; a_class[i] (a->n bytes) what Compare makes of the
+ * pair: GLFSX_JOIN_ONLY without a match, GLFSX_JOIN_TREES when Compare
+ * recurses, GLFSX_JOIN_SAME when Ref.Equals holds (glfs.go:44-46,
+ * blob.go:27-29), GLFSX_JOIN_DIFF otherwise.  Every output is nullable.
+ * Precondition: each side's names are strictly increasing byte-wise (what
+ * status 0 of every line from the decoder vouches for).  If it is broken the
+ * results are unspecified, but every read stays inside the columns, every
+ * write inside the outputs, every match is -1 or a valid index, and the call
+ * returns. */
+int glfsx_tree_join(const glfsx_tree_cols *a, const glfsx_tree_cols *b, int64_t *a_match,
+                    int64_t *b_match, uint8_t *a_class);
+
+/* The same on the GPU: the columns and the outputs in device memory (the two
+ * structs themselves on the host).  One launch whatever the sizes -- one lane
+ * per entry of a and of b, each a binary search over the other side --
+ * enqueued on `stream` and not synchronised.  Without a device:
+ * GLFSX_E_DEVICE. */
+int glfsx_tree_join_device(const glfsx_tree_cols *a, const glfsx_tree_cols *b,
+                           int64_t *d_a_match, int64_t *d_b_match, uint8_t *d_a_class,
+                           void *stream);
+
+/* Gather k entries of two column sets into a new one, on the GPU: output
+ * entry t is a's entry v when v = d_sel[t] >= 0 and b's entry -1 - v when
+ * v < 0; every one of its nine columns is copied (status from a NULL status
+ * column is 0).  name_offs / type_offs receive k + 1 words.  counts[0] = the
+ * bytes of the selected names, counts[1] = of the types: always set.  Every
+ * output is nullable (all NULL: the counts only); k_cap is the capacity in
+ * entries of the per-entry outputs, names_cap / types_cap the bytes at names
+ * / types: if one is too small, or a d_sel value names no entry, the call
+ * returns GLFSX_E_ARG with nothing written.  Four launches whatever k (the
+ * lengths, two scans, the write) enqueued on `stream`, which is synchronised
+ * once to return the counts.  Without a device: GLFSX_E_DEVICE. */
+int glfsx_tree_select_device(const glfsx_tree_cols *a, const glfsx_tree_cols *b,
+                             const int64_t *d_sel, uint64_t k, uint8_t *d_names,
+                             uint64_t names_cap, uint64_t *d_name_offs, uint32_t *d_modes,
+                             uint8_t *d_types, uint64_t types_cap, uint64_t *d_type_offs,
+                             uint8_t *d_roots, uint64_t *d_sizes, uint64_t *d_block_sizes,
+                             uint32_t *d_status, uint64_t k_cap, uint64_t counts[2],
+                             void *stream);
 
 /* BASELINE config 4 in one call (tree.go:250-320 PostTreeMap over n entries
  * whose blobs are glfs.PostBlob'd, machine.go:64), device-resident: blob i
