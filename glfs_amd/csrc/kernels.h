@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "one_classes.h"
+
 namespace glfsx {
 
 // Where ref j of a pass lands: refs + (j / ref_bf) * ref_stride + (j % ref_bf) * 64.
@@ -68,8 +70,9 @@ hipError_t clock_probe(int reset, uint64_t out[2]);
 // since the last reset to out, kLaunchRecWords words each; returns how many
 // were launched since then.  reset: empty the log after reading.  No HIP call.
 size_t pass_log(int reset, uint32_t *out, size_t cap);
-// The same for the aux log: the small-blob launches (k_small, k_small_q) and
-// the decrypt launches (k_decrypt_lines, k_decrypt).
+// The same for the aux log: the small-blob launches (k_small, k_small_q), the
+// decrypt launches (k_decrypt_lines, k_decrypt), the levels of the ragged
+// passes and the one-shot classes.
 size_t aux_log(int reset, uint32_t *out, size_t cap);
 
 // The second half of launch_post alone: ChaCha20 keyed by the DEK already in
@@ -146,11 +149,9 @@ hipError_t launch_post_ragged(const RaggedJob &job, hipStream_t s);
 // descriptor.  src / ctext / ref may be pinned host memory (device pointers
 // of it): the kernel reads the message once and writes ctext and ref
 // straight into the caller's staging, so a post is one launch and a wait.
-// Messages of kMaxOneLen < len <= kMaxMedLen take two launches (launch_med:
-// one workgroup per 64 KiB span, the last-arriving one merges) and need the
-// device scratch below.
-constexpr uint64_t kMaxOneLen = 64ull * 1024;
-constexpr uint64_t kMaxMedLen = 4ull << 20;
+// Messages of kMaxOneLen < len <= kMaxMedLen (one_classes.h) take two launches
+// (the medium pair: one workgroup per 64 KiB span, the last-arriving one
+// merges) and need the device scratch below.
 struct OneDesc {
   const uint8_t *src;  // 16-B aligned, device-accessible
   uint8_t *ctext;      // nullable, device-accessible, 16-B aligned
@@ -160,7 +161,7 @@ struct OneDesc {
   uint32_t cid_keyed;
   uint32_t salt[8];     // DEK key words
   uint32_t cid_key[8];  // CID key words (IV when unkeyed)
-  // launch_med only (device memory): the staged message (len rounded up to
+  // the medium pair only (device memory): the staged message (len rounded up to
   // 64 B), 8 words per 64 KiB span, an arrival counter (zero before the
   // launch, left at zero) and the DEK
   uint8_t *dmsg;
@@ -170,22 +171,13 @@ struct OneDesc {
   uint32_t *flag;
   uint32_t seq;
 };
-// descs: n descriptors in device-accessible memory; max_len bounds their len.
-hipError_t launch_one(const OneDesc *descs, uint32_t n, uint64_t max_len,
-                      hipStream_t s);
-hipError_t launch_med(const OneDesc *descs, uint32_t n, uint64_t max_len,
-                      hipStream_t s);
-// One post, its descriptor passed by value: d.len <= kMaxOneLen (launch_one_v)
-// or kMaxOneLen < d.len <= kMaxMedLen (launch_med_v).
-hipError_t launch_one_v(const OneDesc &d, hipStream_t s);
-hipError_t launch_med_v(const OneDesc &d, hipStream_t s);
 
 // One-shot verified read (one_open_kernels.h; ref.go:113-126 getF with its
 // checks for one block of at most kMaxOneLen bytes): one workgroup stages the
 // ctext from the caller's pinned staging, decrypts it with the ref's DEK and
 // hashes ctext and plaintext side by side; *status = 1 (CID mismatch) | 2
 // (DEK mismatch), 0 when good, written every time; the plaintext is written
-// either way.  The salted form (launch_one_open's `salted`) checks both, the
+// either way.  The salted form (class kOneOpenSalted) checks both, the
 // other one the CID alone (salt is not read, bit 1 never set).  A type of
 // its own: k_one stages OneDesc into LDS by word count.
 struct OneOpenDesc {
@@ -201,12 +193,15 @@ struct OneOpenDesc {
   uint32_t *flag;
   uint32_t seq;
 };
-// descs: n descriptors in device-accessible memory, all salted or all not;
-// max_len bounds their len.
-hipError_t launch_one_open(const OneOpenDesc *descs, uint32_t n, uint64_t max_len, bool salted,
-                           hipStream_t s);
-// One request, its descriptor passed by value.
-hipError_t launch_one_open_v(const OneOpenDesc &d, bool salted, hipStream_t s);
+// One launch (the medium class: its pair) over the n requests of one-shot
+// class c (one_classes.h), as launch_plan.h's one_rec says: h and d are the
+// host's and the device's view of their n descriptors in pinned memory, max_len
+// bounds their len.  One request goes to the kernel by value, from *h.  n == 0
+// launches nothing; a length the class does not take is hipErrorInvalidValue.
+hipError_t launch_one_class(OneClass c, const OneDesc *h, const OneDesc *d, uint32_t n,
+                            uint64_t max_len, hipStream_t s);
+hipError_t launch_one_class(OneClass c, const OneOpenDesc *h, const OneOpenDesc *d, uint32_t n,
+                            uint64_t max_len, hipStream_t s);
 
 // Read side: decrypt n contiguous blocks (bs % 64 == 0; the last one
 // last_len bytes) with the DEKs in bytes [32,64) of refs[j] (dense).

@@ -1,8 +1,8 @@
 // launch_log.h -- which kernel a launch really ran (the test hooks
 // glfsx_debug_pass_log for the bulk passes, glfsx_debug_aux_log for the
-// small-blob and decrypt kernels): the record a launch site appends and the
-// bounded log that keeps them.  Plain C++ and a mutex: no HIP, CPU-tested
-// (tests/c/stream_scratch_test.cpp).
+// small-blob, decrypt, ragged and one-shot kernels): the record a launch site
+// appends and the bounded log that keeps them.  Plain C++ and a mutex: no HIP,
+// CPU-tested (tests/c/stream_scratch_test.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -15,12 +15,21 @@ namespace glfsx {
 
 // Kernel families of the bulk launches (the pass log) ...
 enum : uint32_t { kLaunchPass = 1, kLaunchQuad = 2, kLaunchPassDc = 3, kLaunchOpen = 4 };
-// ... and of the aux log: k_small, k_small_q, k_decrypt_lines, k_decrypt.
+// ... and of the aux log: k_small, k_small_q, k_decrypt_lines, k_decrypt;
+// the three levels of a ragged pass, post or open (k_rag_chunk / k_rag_merge_a
+// / k_rag_merge_b and their k_rag_open_ forms); the one-shot classes (k_one,
+// the k_med_dek + k_med_cid pair, k_one_open; by value or over an array).
 enum : uint32_t {
   kLaunchSmall = 5,
   kLaunchSmallQ = 6,
   kLaunchDecryptLines = 7,
-  kLaunchDecrypt = 8
+  kLaunchDecrypt = 8,
+  kLaunchRagChunk = 9,
+  kLaunchRagMergeA = 10,
+  kLaunchRagMergeB = 11,
+  kLaunchOne = 12,
+  kLaunchMed = 13,
+  kLaunchOneOpen = 14
 };
 
 // A count as a log word: saturated, never truncated.
@@ -30,7 +39,8 @@ inline uint32_t log_word(uint64_t v) { return v < UINT32_MAX ? uint32_t(v) : UIN
 // selection (launch_plan.h) returns it; the launch site runs and logs it.
 // kLaunchRecWords uint32_t, in this order (include/glfsx.h documents it).
 // The aux families use the same ten words (small_rec, lines_rec,
-// decrypt_rec of launch_plan.h; the word use is in include/glfsx.h).
+// decrypt_rec, rag_pass_recs, one_rec of launch_plan.h; the word use is in
+// include/glfsx.h).
 struct LaunchRec {
   uint32_t family;      // kLaunchPass ...
   uint32_t g;           // G; k_quad: quads per workgroup

@@ -2,13 +2,16 @@
 // what shape, as pure functions of the job's sizes, the low bits of its
 // addresses and the tuning values: no HIP call, builds with the host compiler
 // alone, CPU-tested (tests/c/stream_scratch_test.cpp, launch_plan_sweep.cpp).
-// A bulk launch (k_pass, k_quad, k_pass_dc, k_open) is a LaunchRec, which the
-// launch site runs and logs.  Rationale and measurements: DESIGN.md.
+// A launch is a LaunchRec, which its family's one launch site runs and logs:
+// the bulk passes (k_pass, k_quad, k_pass_dc, k_open) in the pass log, the
+// small-blob, decrypt, ragged and one-shot kernels in the aux log.  Rationale
+// and measurements: DESIGN.md.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include "launch_log.h"
+#include "one_classes.h"
 
 #if defined(__HIPCC__)
 #define PLAN_HD __host__ __device__ __forceinline__
@@ -44,9 +47,34 @@ constexpr bool among(const T (&set)[N], uint32_t x) {
 constexpr bool pass_form_ok(uint32_t g, bool chacha, bool aligned, uint32_t form) {
   return form == 2 || (aligned && (form == 0 || (form == 1 && chacha && g >= 4)));
 }
+// The ragged passes (RagKind below: the post's two, the open's three modes):
+// k_rag_chunk<kind == 1, A>, k_rag_open_chunk<kind - 2, A>, the merge levels.
+enum RagKind : uint32_t {
+  kRagPostDek = 0, kRagPostCid = 1, kRagOpen0 = 2, kRagOpen1 = 3, kRagOpen2 = 4
+};
+constexpr int kRagPostKinds[] = {kRagPostDek, kRagPostCid};
+constexpr int kRagOpenKinds[] = {kRagOpen2, kRagOpen1, kRagOpen0};
+constexpr int kRagForms[] = {0, 2};
+constexpr uint32_t kRagMaxGrid = 1u << 20;
+constexpr bool rag_chacha(uint32_t kind) { return kind == kRagPostCid || kind >= kRagOpen1; }
+// The one-shot classes: k_one<QUADS>, k_one_open<QUADS, SALTED>, each by value
+// or over an array; QUADS 16 up to kOneQuads16Max bytes.  The medium pair: 64.
+constexpr int kOneQuads[] = {16, 64};
+constexpr uint64_t kOneQuads16Max = 16 * 1024;
+constexpr bool aux_launchable(const LaunchRec &r) {
+  if (r.family >= kLaunchRagChunk && r.family <= kLaunchRagMergeB)
+    return (among(kRagPostKinds, r.g) || among(kRagOpenKinds, r.g)) &&
+           r.chacha == rag_chacha(r.g) && !r.aligned &&
+           (r.family == kLaunchRagChunk ? among(kRagForms, r.form) : r.form == 0);
+  if (!r.aligned || r.form || r.fine_div > 1) return false;
+  if (r.family == kLaunchMed) return r.g == 64 && r.chacha;
+  if (r.family == kLaunchOne) return among(kOneQuads, r.g) && r.chacha;
+  return r.family == kLaunchOneOpen && among(kOneQuads, r.g);
+}
 constexpr bool launchable(const LaunchRec &r) {
   const bool both = r.chacha == 1 && r.form == 2;  // k_pass_dc, k_open: both passes, form 2
   if (r.chacha > 1 || r.aligned > 1) return false;
+  if (r.family >= kLaunchRagChunk) return aux_launchable(r);
   if (r.family == kLaunchPass)
     return among(kPassGs, r.g) && pass_form_ok(r.g, r.chacha, r.aligned, r.form);
   if (r.family == kLaunchQuad)
@@ -244,21 +272,66 @@ inline bool open_rec(uint64_t n, uint64_t bs, bool salted, bool aligned, int rou
 }
 
 // ---- The families outside the pass log ----
-// The small-blob kernels (k_small, k_small_q) and the read-side decrypt
-// (k_decrypt_lines, k_decrypt) append to a second log, the aux log
-// (glfsx_debug_aux_log), at their launch sites: small_rec, lines_rec,
-// decrypt_rec below; tests/test_gpu_small_decrypt_matrix.py has a row per
-// instantiation.  The ragged chunk passes (rag_chunk_plan) and the one-shot
-// ladders (oneshot.cpp) stay outside both logs.
+// The small-blob kernels (k_small, k_small_q), the read-side decrypt
+// (k_decrypt_lines, k_decrypt), the levels of a ragged pass and the one-shot
+// classes append to a second log, the aux log (glfsx_debug_aux_log), at their
+// launch sites: small_rec, lines_rec, decrypt_rec, rag_pass_recs and one_rec
+// below; tests/test_gpu_small_decrypt_matrix.py has a row per instantiation.
 
 struct GridForm {
   uint32_t grid, form;
 };
-// The ragged chunk passes: a workgroup per tile of 256 chunks, at most 2^20.
-// Not logged.
+inline uint32_t capped_grid(uint64_t wgs, uint32_t slots) {
+  return uint32_t(slots && slots < wgs ? slots : wgs);
+}
+
+// One pass of a ragged call (RagKind): the post's DEK or CID pass, or the open
+// in mode 0 (the CID alone), 1 (and the plaintext) or 2 (and the DEK check).
+// Its chunk level: a workgroup per tile of 256 chunks, at most 2^20;
+// latency-bound launches in form 0.  Called by rag_pass_recs alone.
 inline GridForm rag_chunk_plan(uint64_t total, uint32_t latency_wgs) {
   const uint64_t tiles = (total + 255) >> 8;
-  return {uint32_t(tiles < (1u << 20) ? tiles : 1u << 20), arx_form(tiles, latency_wgs)};
+  return {capped_grid(tiles, kRagMaxGrid), arx_form(tiles, latency_wgs)};
+}
+// Its launches, from the plan's totals (tot: chunks, merge groups, messages
+// of more than 256 chunks): the chunk level, then the merge levels that have
+// work, a workgroup per group (A) or message (B), at most 2^20.
+struct RagPlan {
+  uint32_t n;
+  LaunchRec rec[3];
+};
+inline RagPlan rag_pass_recs(const uint64_t tot[3], uint32_t kind, uint32_t latency_wgs) {
+  const GridForm c = rag_chunk_plan(tot[0], latency_wgs);
+  const uint32_t chacha = rag_chacha(kind);
+  RagPlan p{1, {{kLaunchRagChunk, kind, chacha, 0, c.form, 0, c.grid, 0, log_word(tot[0]), 0}}};
+  for (uint32_t level = 1; level <= 2; ++level)
+    if (tot[level])
+      p.rec[p.n++] = {kLaunchRagChunk + level, kind, chacha, 0, 0, 0,
+                      capped_grid(tot[level], kRagMaxGrid), 0, log_word(tot[level]), 0};
+  return p;
+}
+
+// One launch over the n requests of one-shot class c, none longer than
+// max_len: k_one or k_one_open with 16 quads of four lanes up to
+// kOneQuads16Max bytes and 64 above, or the medium pair (k_med_dek, then
+// k_med_cid, on the same grid: a workgroup per 64 KiB span).  One request
+// goes by value (fine_div 1), more through the descriptor array.  False: a
+// length the class does not take.  r->grid 0: nothing to launch.
+inline bool one_rec(OneClass c, uint32_t n, uint64_t max_len, LaunchRec *r) {
+  *r = LaunchRec{};
+  if (n == 0) return true;
+  const bool med = c == kOneMed;
+  if (max_len > (med ? kMaxMedLen : kMaxOneLen) || (med && max_len <= kMaxOneLen)) return false;
+  const uint32_t quads = max_len <= kOneQuads16Max ? 16 : 64;
+  const uint32_t wmax = med ? uint32_t((max_len + 65535) >> 16) : 1u;
+  *r = {med ? kLaunchMed : c == kOneSmall ? kLaunchOne : kLaunchOneOpen, quads,
+        c != kOneOpen, 1, 0, 0, n * wmax, n == 1, uint32_t(max_len), n};
+  return true;
+}
+// Its workgroup, the kernels' __launch_bounds__: four lanes per quad, and as
+// many again for the salted open's second tree.
+constexpr uint32_t one_block(const LaunchRec &r) {
+  return r.g * (r.family == kLaunchOneOpen && r.chacha ? 8 : 4);
 }
 
 // One pass over n small blobs of at most max_len bytes.  g: chunks per blob
@@ -287,9 +360,6 @@ inline SmallPlan small_plan(uint64_t n, uint64_t max_len, bool chacha, uint32_t 
   p.items = p.n_coarse + (n - (p.n_coarse << 6) + bpi - 1) / bpi;
   p.wgs = (p.items + 3) / 4;
   return p;
-}
-inline uint32_t capped_grid(uint64_t wgs, uint32_t slots) {
-  return uint32_t(slots && slots < wgs ? slots : wgs);
 }
 // The aux-log record of a small-blob launch: grid as launched (k_small_q:
 // after capped_grid), n_coarse, items and n saturated.

@@ -3,7 +3,7 @@
 // requests' kinds and lengths: no HIP, no state.
 //
 // A batch mixes posts and verified reads ("opens").  Each class present gets
-// one launch over a contiguous descriptor range:
+// one launch (launch_plan.h one_rec) over a contiguous descriptor range:
 //   posts, lengths <= small_max          the post array, [0, count)
 //   posts, longer (two launches each)    the post array, behind the small ones
 //   opens without a DEK check            the open array, [0, count)
@@ -18,6 +18,11 @@ namespace glfsx {
 
 enum OneClass : uint8_t { kOneSmall = 0, kOneMed = 1, kOneOpen = 2, kOneOpenSalted = 3 };
 constexpr int kOneClasses = 4;
+
+// The classes' length limits: one launch up to kMaxOneLen (posts and opens),
+// the medium posts' two launches up to kMaxMedLen (kernels.h: OneDesc).
+constexpr uint64_t kMaxOneLen = 64ull * 1024;
+constexpr uint64_t kMaxMedLen = 4ull << 20;
 
 struct OneItem {
   bool open;     // a verified read, else a post

@@ -11,7 +11,7 @@
 namespace glfsx {
 namespace host {
 
-// ---- One-shot posts (launch_one) ----
+// ---- One-shot posts (launch_one_class) ----
 // A post of one message of at most kMaxMedLen bytes from host memory: the
 // bytes sit in pinned staging, the kernel reads them there and writes ctext
 // and ref straight back into pinned staging, then sets the request's flag
@@ -119,8 +119,8 @@ void pending_push(OnePoster *P, OneReq *r) {
 std::atomic<uint32_t> g_one_drop{~0u};
 
 // The batch's classes (one_classes.h) each in their own descriptor range,
-// and one launch per class present on the lane's stream: k_one over the small
-// posts, launch_med (two kernels) over the medium ones, k_one_open over the
+// and one launch_one_class per class present on the lane's stream: k_one over
+// the small posts, the medium pair over the medium ones, k_one_open over the
 // opens without and with a DEK check; request k's flag is lane.h_flag[k], set
 // to `seq` when its results are in place.
 int one_launch(OneLane &L, const std::vector<OneReq *> &batch, uint32_t seq) {
@@ -129,8 +129,7 @@ int one_launch(OneLane &L, const std::vector<OneReq *> &batch, uint32_t seq) {
   for (size_t k = 0; k < batch.size(); ++k)
     items[k] = OneItem{batch[k]->open, batch[k]->salted, batch[k]->len()};
   const OneLayout lay = one_layout(items.data(), items.size(), kMaxOneLen);
-  const uint32_t ns = lay.count[kOneSmall], nm = lay.count[kOneMed];
-  if (nm) {
+  if (const uint32_t nm = lay.count[kOneMed]) {
     if (int e = L.med_msg.ensure(lay.med_bytes)) return e;
     if (int e = L.med_aux.ensure(nm * kMedAuxWords * 4)) return e;
     if (L.med_aux.cap > L.aux_zeroed) {  // new buffer: counters must start at zero
@@ -162,22 +161,12 @@ int one_launch(OneLane &L, const std::vector<OneReq *> &batch, uint32_t seq) {
     }
     L.h_desc[slot] = d;
   }
-  // a launch of one request (of any class) passes its descriptor by value
-  // instead of through the pinned descriptor array
-  if (ns == 1)
-    HIP_TRY(launch_one_v(L.h_desc[0], L.s));
-  else if (ns)
-    HIP_TRY(launch_one(L.d_desc, ns, lay.max_len[kOneSmall], L.s));
-  if (nm == 1)
-    HIP_TRY(launch_med_v(L.h_desc[ns], L.s));
-  else if (nm)
-    HIP_TRY(launch_med(L.d_desc + ns, nm, lay.max_len[kOneMed], L.s));
-  for (const OneClass c : {kOneOpen, kOneOpenSalted}) {
+  for (const OneClass c : {kOneSmall, kOneMed, kOneOpen, kOneOpenSalted}) {
     const uint32_t n = lay.count[c], at = lay.start[c];
-    if (n == 1)
-      HIP_TRY(launch_one_open_v(L.h_odesc[at], c == kOneOpenSalted, L.s));
-    else if (n)
-      HIP_TRY(launch_one_open(L.d_odesc + at, n, lay.max_len[c], c == kOneOpenSalted, L.s));
+    if (c == kOneSmall || c == kOneMed)
+      HIP_TRY(launch_one_class(c, L.h_desc + at, L.d_desc + at, n, lay.max_len[c], L.s));
+    else
+      HIP_TRY(launch_one_class(c, L.h_odesc + at, L.d_odesc + at, n, lay.max_len[c], L.s));
   }
   HIP_TRY(hipEventRecord(L.ev, L.s));
   return 0;

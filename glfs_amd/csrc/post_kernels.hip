@@ -70,8 +70,10 @@ Knobs knobs() {
 // a launch on another thread may outlive the process's static destructors.
 LaunchLog &g_launch_log = *new LaunchLog();
 // The aux log (glfsx_debug_aux_log), a log of its own so that the pass log
-// keeps its content: the small-blob launches (launch_small_pass) and the
-// decrypt launches (decrypt_with, the latency-mode posts' keystream leg too).
+// keeps its content: the small-blob launches (launch_small_pass), the
+// decrypt launches (decrypt_with, the latency-mode posts' keystream leg too),
+// the ragged levels (launch_rag_levels) and the one-shot classes
+// (launch_one_class).
 LaunchLog &g_aux_log = *new LaunchLog();
 
 // f(integral_constant<int, G>) for the G of Gs (a constexpr array of
@@ -588,25 +590,28 @@ static hipError_t rag_plan(RArgs &a, RagBufs ScratchSlot::*set, uint32_t cv_word
   return e;
 }
 
-// One pass of the ragged post: the chunks, then the merge levels that have
-// work (tot: chunks, merge groups, messages of more than 256 chunks).
-template <bool CHACHA>
-static hipError_t launch_rag_pass(RArgs a, const uint64_t tot[3], hipStream_t s) {
-  a.total = tot[0];
-  const GridForm p = rag_chunk_plan(tot[0], knobs().latency_wgs);
-  if (p.form == 0)
-    hipLaunchKernelGGL((k_rag_chunk<CHACHA, 0>), dim3(p.grid), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((k_rag_chunk<CHACHA, 2>), dim3(p.grid), dim3(256), 0, s, a);
-  hipError_t e = hipGetLastError();
-  auto merge = [&](auto k, uint64_t total) {  // a level that has work
-    a.total = total;
-    hipLaunchKernelGGL(k, dim3(capped_grid(total, 1u << 20)), dim3(256), 0, s, a);
-    return hipGetLastError();
-  };
-  if (e == hipSuccess && tot[1]) e = merge(k_rag_merge_a, tot[1]);
-  if (e == hipSuccess && tot[2]) e = merge(k_rag_merge_b, tot[2]);
-  return e;
+// The kernel of one level of a ragged pass, r.  Defined behind their callers,
+// launch_post_ragged and launch_open_ragged: the compiler emits kernels in the
+// order it meets them, and the code object keeps the order it had.
+static hipError_t rag_level(const LaunchRec &r, const RArgs &a, hipStream_t s);
+static hipError_t rag_level(const LaunchRec &r, const ROArgs &a, hipStream_t s);
+static RArgs &rag_args(RArgs &a) { return a; }
+static RArgs &rag_args(ROArgs &a) { return a.r; }
+
+// The one launch-and-log site of the ragged levels: the records of one pass
+// (rag_pass_recs over the plan's totals `tot`), in order.
+template <class Args>
+static hipError_t launch_rag_levels(const RagPlan &p, const uint64_t tot[3], Args a, hipStream_t s) {
+  for (uint32_t i = 0; i < p.n; ++i) {
+    const LaunchRec &r = p.rec[i];
+    if (!launchable(r)) return hipErrorInvalidValue;
+    rag_args(a).total = tot[r.family - kLaunchRagChunk];
+    hipError_t e = rag_level(r, a, s);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (g_aux_log.on()) g_aux_log.append(r);
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_post_ragged(const RaggedJob &job, hipStream_t s) {
@@ -627,12 +632,26 @@ hipError_t launch_post_ragged(const RaggedJob &job, hipStream_t s) {
   for (int i = 0; i < 8; ++i) a.key[i] = job.salt[i];
   a.base = kKeyed;
   a.out_off = 32;
-  e = launch_rag_pass<false>(a, totals, s);
+  e = launch_rag_levels(rag_pass_recs(totals, kRagPostDek, knobs().latency_wgs), totals, a, s);
   if (e != hipSuccess) return e;
   for (int i = 0; i < 8; ++i) a.key[i] = job.cid_key[i];
   a.base = job.cid_keyed ? kKeyed : 0u;
   a.out_off = 0;
-  return launch_rag_pass<true>(a, totals, s);
+  return launch_rag_levels(rag_pass_recs(totals, kRagPostCid, knobs().latency_wgs), totals, a, s);
+}
+
+static hipError_t rag_level(const LaunchRec &r, const RArgs &a, hipStream_t s) {
+  const dim3 grid(r.grid), block(256);
+  return with_g<kRagPostKinds>(r.g, [&](auto K) {
+    if (r.family == kLaunchRagChunk)
+      return with_g<kRagForms>(r.form, [&](auto A) {
+        hipLaunchKernelGGL((k_rag_chunk<K() == kRagPostCid, A()>), grid, block, 0, s, a);
+        return hipSuccess;
+      });
+    if (r.family == kLaunchRagMergeA) hipLaunchKernelGGL(k_rag_merge_a, grid, block, 0, s, a);
+    if (r.family == kLaunchRagMergeB) hipLaunchKernelGGL(k_rag_merge_b, grid, block, 0, s, a);
+    return hipSuccess;
+  });
 }
 
 #if GLFSX_ONE_TIMING
@@ -678,62 +697,61 @@ hipError_t debug_wgtime(uint64_t *out) {
 }
 #endif
 
-// k_med_dek then k_med_cid (or their _v forms) over n messages of at most
-// len bytes, a workgroup per 64 KiB.
-template <class K, class A>
-static hipError_t med_launch(K dek, K cid, uint32_t n, uint64_t len, const A &a, hipStream_t s) {
-  if (len > kMaxMedLen || len <= kMaxOneLen) return hipErrorInvalidValue;
-  const uint32_t wmax = uint32_t((len + 65535) >> 16);
-  hipLaunchKernelGGL(dek, dim3(n * wmax), dim3(256), 0, s, a, wmax);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(cid, dim3(n * wmax), dim3(256), 0, s, a, wmax);
-  return hipGetLastError();
-}
-hipError_t launch_med(const OneDesc *descs, uint32_t n, uint64_t max_len, hipStream_t s) {
-  return n ? med_launch(k_med_dek, k_med_cid, n, max_len, descs, s) : hipSuccess;
-}
-hipError_t launch_med_v(const OneDesc &d, hipStream_t s) {
-  return med_launch(k_med_dek_v, k_med_cid_v, 1, d.len, d, s);
-}
+// ---- The one-shot classes (one_kernels.h, one_open_kernels.h) ----
 
-// k_one (or k_one_v): 16 chunks a workgroup of 64 lanes up to 16 KiB, else 64 of 256.
-template <class K, class A>
-static hipError_t one_launch(K k16, K k64, uint32_t n, uint64_t len, const A &a, hipStream_t s) {
-  if (len > kMaxOneLen) return hipErrorInvalidValue;
-  if (len <= 16 * 1024)
-    hipLaunchKernelGGL(k16, dim3(n), dim3(64), 0, s, a);
+// ka over the array at d, or -- r goes by value -- kv over the one descriptor
+// at h.
+template <class KA, class KV, class D, class... X>
+static hipError_t one_go(const LaunchRec &r, KA ka, KV kv, const D *h, const D *d, hipStream_t s,
+                         X... x) {
+  if (r.fine_div)
+    hipLaunchKernelGGL(kv, dim3(r.grid), dim3(one_block(r)), 0, s, *h, x...);
   else
-    hipLaunchKernelGGL(k64, dim3(n), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(ka, dim3(r.grid), dim3(one_block(r)), 0, s, d, x...);
   return hipGetLastError();
 }
-hipError_t launch_one(const OneDesc *descs, uint32_t n, uint64_t max_len, hipStream_t s) {
-  return n ? one_launch(k_one<16>, k_one<64>, n, max_len, descs, s) : hipSuccess;
+// The kernels of a launchable r, [QUADS == 64]: kOneQuads.
+static hipError_t one_kernels(const LaunchRec &r, const OneDesc *h, const OneDesc *d,
+                              hipStream_t s) {
+  if (r.family == kLaunchOne) {
+    void (*const ka[])(const OneDesc *) = {k_one<16>, k_one<64>};
+    void (*const kv[])(const OneDesc) = {k_one_v<16>, k_one_v<64>};
+    return one_go(r, ka[r.g == 64], kv[r.g == 64], h, d, s);
+  }
+  if (r.family != kLaunchMed) return hipErrorInvalidValue;
+  const uint32_t wmax = r.grid / r.n;  // workgroups per message, one per 64 KiB
+  const hipError_t e = one_go(r, k_med_dek, k_med_dek_v, h, d, s, wmax);
+  return e != hipSuccess ? e : one_go(r, k_med_cid, k_med_cid_v, h, d, s, wmax);
 }
-hipError_t launch_one_v(const OneDesc &d, hipStream_t s) {
-  return one_launch(k_one_v<16>, k_one_v<64>, 1, d.len, d, s);
+static hipError_t one_kernels(const LaunchRec &r, const OneOpenDesc *h, const OneOpenDesc *d,
+                              hipStream_t s) {
+  if (r.family != kLaunchOneOpen) return hipErrorInvalidValue;
+  void (*const ka[2][2])(const OneOpenDesc *) = {{k_one_open<16, true>, k_one_open<64, true>},
+                                                 {k_one_open<16, false>, k_one_open<64, false>}};
+  void (*const kv[2][2])(const OneOpenDesc) = {{k_one_open_v<16, true>, k_one_open_v<64, true>},
+                                               {k_one_open_v<16, false>, k_one_open_v<64, false>}};
+  return one_go(r, ka[!r.chacha][r.g == 64], kv[!r.chacha][r.g == 64], h, d, s);
 }
 
-// k_one_open (or _v): 16 quads up to 16 KiB, else 64; four lanes per quad,
-// two trees when salted.
-template <class K, class A>
-static hipError_t one_open_launch(K k16s, K k64s, K k16, K k64, uint32_t n, uint64_t len,
-                                  bool salted, const A &a, hipStream_t s) {
-  if (len > kMaxOneLen) return hipErrorInvalidValue;
-  const bool small = len <= 16 * 1024;
-  const K k = salted ? (small ? k16s : k64s) : (small ? k16 : k64);
-  hipLaunchKernelGGL(k, dim3(n), dim3((small ? 16 : 64) * (salted ? 8 : 4)), 0, s, a);
-  return hipGetLastError();
+// The one launch-and-log site of the one-shot classes: one_rec's record.
+template <class D>
+static hipError_t launch_one_rec(OneClass c, const D *h, const D *d, uint32_t n, uint64_t max_len,
+                                 hipStream_t s) {
+  LaunchRec r;
+  if (!one_rec(c, n, max_len, &r)) return hipErrorInvalidValue;
+  if (!r.grid) return hipSuccess;
+  if (!launchable(r)) return hipErrorInvalidValue;
+  const hipError_t e = one_kernels(r, h, d, s);
+  if (e == hipSuccess && g_aux_log.on()) g_aux_log.append(r);
+  return e;
 }
-hipError_t launch_one_open(const OneOpenDesc *descs, uint32_t n, uint64_t max_len, bool salted,
-                           hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  return one_open_launch(k_one_open<16, true>, k_one_open<64, true>, k_one_open<16, false>,
-                         k_one_open<64, false>, n, max_len, salted, descs, s);
+hipError_t launch_one_class(OneClass c, const OneDesc *h, const OneDesc *d, uint32_t n,
+                            uint64_t max_len, hipStream_t s) {
+  return launch_one_rec(c, h, d, n, max_len, s);
 }
-hipError_t launch_one_open_v(const OneOpenDesc &d, bool salted, hipStream_t s) {
-  return one_open_launch(k_one_open_v<16, true>, k_one_open_v<64, true>, k_one_open_v<16, false>,
-                         k_one_open_v<64, false>, 1, d.len, salted, d, s);
+hipError_t launch_one_class(OneClass c, const OneOpenDesc *h, const OneOpenDesc *d, uint32_t n,
+                            uint64_t max_len, hipStream_t s) {
+  return launch_one_rec(c, h, d, n, max_len, s);
 }
 
 hipError_t launch_decrypt(const uint8_t *ctext, uint8_t *ptext, uint64_t n, uint64_t bs,
@@ -849,26 +867,6 @@ hipError_t launch_open(const OpenJob &job, hipStream_t s) {
 
 // ---- The ragged open (ragged_open_kernels.h) ----
 
-// The chunk pass and the merge levels that have work, in mode MODE.
-template <int MODE>
-static hipError_t launch_rag_open_pass(ROArgs a, const uint64_t tot[3], hipStream_t s) {
-  a.r.total = tot[0];
-  const GridForm p = rag_chunk_plan(tot[0], knobs().latency_wgs);
-  if (p.form == 0)
-    hipLaunchKernelGGL((k_rag_open_chunk<MODE, 0>), dim3(p.grid), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((k_rag_open_chunk<MODE, 2>), dim3(p.grid), dim3(256), 0, s, a);
-  hipError_t e = hipGetLastError();
-  auto merge = [&](auto k, uint64_t total) {  // a level that has work
-    a.r.total = total;
-    hipLaunchKernelGGL(k, dim3(capped_grid(total, 1u << 20)), dim3(256), 0, s, a);
-    return hipGetLastError();
-  };
-  if (e == hipSuccess && tot[1]) e = merge(k_rag_open_merge_a<MODE == 2>, tot[1]);
-  if (e == hipSuccess && tot[2]) e = merge(k_rag_open_merge_b<MODE == 2>, tot[2]);
-  return e;
-}
-
 hipError_t launch_open_ragged(const OpenRaggedJob &job, hipStream_t s) {
   if (job.n == 0) return hipSuccess;
   if (job.max_len > kMaxRaggedLen) return hipErrorInvalidValue;
@@ -892,9 +890,25 @@ hipError_t launch_open_ragged(const OpenRaggedJob &job, hipStream_t s) {
     a.salt[i] = job.salt[i];
   }
   a.r.base = job.cid_keyed ? kKeyed : 0u;
-  if (job.salted) return launch_rag_open_pass<2>(a, totals, s);
-  if (job.ptext) return launch_rag_open_pass<1>(a, totals, s);
-  return launch_rag_open_pass<0>(a, totals, s);
+  const RagKind kind = job.salted ? kRagOpen2 : job.ptext ? kRagOpen1 : kRagOpen0;
+  return launch_rag_levels(rag_pass_recs(totals, kind, knobs().latency_wgs), totals, a, s);
+}
+
+static hipError_t rag_level(const LaunchRec &r, const ROArgs &a, hipStream_t s) {
+  const dim3 grid(r.grid), block(256);
+  return with_g<kRagOpenKinds>(r.g, [&](auto K) {
+    constexpr int MODE = K() - kRagOpen0;
+    if (r.family == kLaunchRagChunk)
+      return with_g<kRagForms>(r.form, [&](auto A) {
+        hipLaunchKernelGGL((k_rag_open_chunk<MODE, A()>), grid, block, 0, s, a);
+        return hipSuccess;
+      });
+    if (r.family == kLaunchRagMergeA)
+      hipLaunchKernelGGL(k_rag_open_merge_a<MODE == 2>, grid, block, 0, s, a);
+    if (r.family == kLaunchRagMergeB)
+      hipLaunchKernelGGL(k_rag_open_merge_b<MODE == 2>, grid, block, 0, s, a);
+    return hipSuccess;
+  });
 }
 
 }  // namespace glfsx

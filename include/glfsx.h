@@ -193,9 +193,10 @@ int glfsx_debug_pass_log(int reset, uint32_t *out, size_t cap, size_t *n);
 
 /* Test hook (no reference counterpart): the same for the kernels outside the
  * pass log, in a log of its own (the pass log's content does not change):
- * the small-blob kernels of glfsx_post_blobs[_device] / glfsx_post_tree_device
- * and the decrypt kernels of glfsx_decrypt_batch[_device], the Reader, the
- * composed verified read and the keystream leg of latency-bound posts.  Off
+ * the small-blob kernels of glfsx_post_blobs[_device] / glfsx_post_tree_device,
+ * the decrypt kernels of glfsx_decrypt_batch[_device], the Reader, the
+ * composed verified read and the keystream leg of latency-bound posts, the
+ * levels of the ragged post and open, and the one-shot poster's launches.  Off
  * until first called; signature, capacity and semantics as
  * glfsx_debug_pass_log.  A record is the same GLFSX_PASS_LOG_WORDS words; a
  * count above UINT32_MAX is stored as UINT32_MAX, never truncated:
@@ -215,12 +216,46 @@ int glfsx_debug_pass_log(int reset, uint32_t *out, size_t cap, size_t *n);
  *   GLFSX_LOG_DECRYPT (k_decrypt, a lane per 64-byte keystream block):
  *     [1] 0  [2] 1  [3] 1 when both buffers are 16-byte aligned  [4] 0  [5] 0
  *     [6] grid  [7] 0  [8] first_kb: the first keystream block it takes (the
- *         ones before it went through k_decrypt_lines)  [9] blocks */
+ *         ones before it went through k_decrypt_lines)  [9] blocks
+ * and the two families that post and open unequal or single messages:
+ *   GLFSX_LOG_RAG_CHUNK, _RAG_MERGE_A, _RAG_MERGE_B: the levels of one pass of
+ *   glfsx_post_ragged_device / glfsx_open_ragged_device (and the blob routes
+ *   built on them), in launch order; a merge level appears only when it has
+ *   work (A: a message of more than one chunk, B: of more than 256):
+ *     [1] the pass: 0 the post's DEK pass (k_rag_chunk<false, form>), 1 its
+ *         CID pass (k_rag_chunk<true, form>), 2 + mode the open
+ *         (k_rag_open_chunk<mode, form>; mode 0 the CID alone, 1 with the
+ *         plaintext, 2 with the DEK check too -- k_rag_open_merge_*<true>)
+ *     [2] 1 when the pass runs ChaCha20 (passes 1, 3, 4)  [3] 0
+ *     [4] ARX form of the chunk level, 0 or 2 (merge levels 0)  [5] 0
+ *     [6] grid (at most 2^20)  [7] 0
+ *     [8] the level's items: chunks, merge groups, messages of more than 256
+ *         chunks  [9] 0
+ *   GLFSX_LOG_ONE (k_one / k_one_v), GLFSX_LOG_MED (the pair k_med_dek +
+ *   k_med_cid or their _v forms: one record for the two launches) and
+ *   GLFSX_LOG_ONE_OPEN (k_one_open / k_one_open_v): one launch of the
+ *   coalescing one-shot poster over the requests of one class -- glfsx_post,
+ *   glfsx_open, glfsx_create of one block, a Writer's few last blocks and its
+ *   index nodes:
+ *     [1] QUADS: 16 up to 16 KiB, else 64 (GLFSX_LOG_MED: 64)
+ *     [2] GLFSX_LOG_ONE_OPEN: SALTED, 1 when the DEK is checked too; else 1
+ *     [3] 1  [4] 0  [5] 0
+ *     [6] grid: a workgroup per request (GLFSX_LOG_MED: per 64 KiB span of
+ *         the longest request)
+ *     [7] 1: the one request's descriptor went by value (the _v kernel);
+ *         0: the descriptor array
+ *     [8] the longest request, bytes  [9] requests */
 enum {
   GLFSX_LOG_SMALL = 5,
   GLFSX_LOG_SMALL_Q = 6,
   GLFSX_LOG_DECRYPT_LINES = 7,
-  GLFSX_LOG_DECRYPT = 8
+  GLFSX_LOG_DECRYPT = 8,
+  GLFSX_LOG_RAG_CHUNK = 9,
+  GLFSX_LOG_RAG_MERGE_A = 10,
+  GLFSX_LOG_RAG_MERGE_B = 11,
+  GLFSX_LOG_ONE = 12,
+  GLFSX_LOG_MED = 13,
+  GLFSX_LOG_ONE_OPEN = 14
 };
 int glfsx_debug_aux_log(int reset, uint32_t *out, size_t cap, size_t *n);
 

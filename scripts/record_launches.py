@@ -194,5 +194,145 @@ def main(path):
     print("%d calls, %d distinct kernels" % (len(lines), len(kernels)))
 
 
+# ---- the ragged passes and the one-shot classes (glfsx_debug_aux_log) ----
+# tests/golden/aux_launch_records.txt is main_aux's output from a build of the
+# old launchers (launch_rag_pass, launch_rag_open_pass, the one / med /
+# one-open ladders) with nothing added but an append after each launch of the
+# record of what that launcher had just launched, written out by hand there.
+# That build was never a commit of its own (the launchers went away in the
+# commit that added this function), so git cannot reproduce the fixture; what
+# can be repeated is the check that matters from here on: a run of this
+# function at any later commit must reproduce the file byte for byte.
+# launch_plan_sweep replays it against rag_pass_recs and one_rec.  The rows
+# with two requests exist for the post classes only (a Writer's Finish): no
+# entry point opens several blocks in one call.  A line is one ragged pass,
+#   R chunks groups large kind latency_wgs nrec <records>
+# (kind: 0 the post's DEK pass, 1 its CID pass, 2 + mode the open), or one
+# one-shot class launch,
+#   O class n max_len nrec <records>
+# (class: OneClass of one_classes.h).  The inputs are what this script asked
+# for, never read back from the records.
+RAG_CHUNK, RAG_A, RAG_B, ONE, MED, ONE_OPEN = 9, 10, 11, 12, 13, 14
+ONE_SMALL, ONE_MED, ONE_OPEN_CLS, ONE_OPEN_SALTED = 0, 1, 2, 3
+
+
+def rag_totals(lens):
+    c = [max(1, -(-ln // 1024)) for ln in lens]
+    return (sum(c), sum(-(-x // 256) for x in c if x > 1), sum(x > 256 for x in c))
+
+
+def rag_cases():
+    big = 16 * MIB
+    return [
+        [1000],                                  # one chunk: no merge level
+        [0, 1, 1024, 5],                         # one-chunk messages only
+        [1, 2000, 1024],                         # level A alone
+        [256 * KIB, 1025],                       # 256 chunks: still no level B
+        [256 * KIB + 1],                         # 257 chunks: both levels
+        [300 * KIB, 7, 5 * MIB + 77, 2048],
+        [255 * KIB, 1024],                       # 256 chunks in all: one tile
+        [255 * KIB, 1025],                       # 257: two tiles
+        [big] * 8,                               # 512 tiles: the default latency bound
+        [big] * 8 + [1],                         # 513 tiles
+    ]
+
+
+def aux_take(N, buf, count):
+    N.check(N.lib.glfsx_debug_aux_log(1, buf, 64, ctypes.byref(count)))
+    assert count.value <= 64, count.value
+    return [list(buf[WORDS * i:WORDS * i + WORDS]) for i in range(count.value)]
+
+
+def main_aux(path):
+    import torch
+    from glfs_amd import _native as N
+    assert torch.cuda.is_available()
+    N.set_device(0)
+    old = (N.set_latency_wgs(512), N.set_open_route(0))
+    buf = (ctypes.c_uint32 * (WORDS * 64))()
+    count = ctypes.c_size_t()
+    lines = []
+
+    def row(head, recs):
+        lines.append(" ".join(str(x) for x in list(head) + [len(recs)] + sum(recs, [])))
+
+    # ragged: the post's two passes and the open in its three modes
+    for lens in rag_cases():
+        offs, o = [], 0
+        for ln in lens:
+            offs.append(o)
+            o += (ln + 63) & ~63
+        n, tot = len(lens), rag_totals(lens)
+        data = torch.empty(o + 64, dtype=torch.uint8, device="cuda")
+        out = torch.empty(o + 64, dtype=torch.uint8, device="cuda")
+        refs = torch.zeros(64 * n, dtype=torch.uint8, device="cuda")
+        status = torch.empty(n, dtype=torch.int32, device="cuda")
+        do = torch.tensor(offs, dtype=torch.int64, device="cuda")
+        dl = torch.tensor(lens, dtype=torch.int64, device="cuda")
+        for lat in (512, 0, 1):
+            N.set_latency_wgs(lat)
+            torch.cuda.synchronize()
+            N.check(N.lib.glfsx_debug_aux_log(1, None, 0, None))
+            N.check(N.lib.glfsx_post_ragged_device(SALT, None, data.data_ptr(), do.data_ptr(),
+                                                   dl.data_ptr(), n, max(lens), out.data_ptr(),
+                                                   refs.data_ptr(), None))
+            torch.cuda.synchronize()
+            log = aux_take(N, buf, count)
+            assert all(r[0] in (RAG_CHUNK, RAG_A, RAG_B) for r in log), log
+            starts = [i for i, r in enumerate(log) if r[0] == RAG_CHUNK]
+            assert len(starts) == 2, log
+            row(("R",) + tot + (0, lat), log[:starts[1]])
+            row(("R",) + tot + (1, lat), log[starts[1]:])
+            for mode in (0, 1, 2):
+                N.check(N.lib.glfsx_debug_aux_log(1, None, 0, None))
+                N.check(N.lib.glfsx_open_ragged_device(
+                    SALT if mode == 2 else None, None, data.data_ptr(), do.data_ptr(),
+                    dl.data_ptr(), n, max(lens), refs.data_ptr(),
+                    out.data_ptr() if mode else None, status.data_ptr(), None))
+                torch.cuda.synchronize()
+                row(("R",) + tot + (2 + mode, lat), aux_take(N, buf, count))
+        del data, out
+    N.set_latency_wgs(512)
+
+    # one-shot, one request: glfsx_post and glfsx_open pass the descriptor by value
+    host = ctypes.create_string_buffer(4 * MIB + 64)
+    h_ct = ctypes.create_string_buffer(4 * MIB + 64)
+    ref = ctypes.create_string_buffer(64)
+    st = ctypes.c_uint32()
+    for ln in (0, 16 * KIB, 16 * KIB + 1, 64 * KIB, 64 * KIB + 1, 4 * MIB):
+        N.check(N.lib.glfsx_debug_aux_log(1, None, 0, None))
+        N.check(N.lib.glfsx_post(SALT, host, ln, h_ct, ref, None))
+        row(("O", ONE_SMALL if ln <= 64 * KIB else ONE_MED, 1, ln), aux_take(N, buf, count))
+        if ln > 64 * KIB:
+            continue
+        for salted in (0, 1):
+            N.check(N.lib.glfsx_debug_aux_log(1, None, 0, None))
+            rc = N.lib.glfsx_open(SALT if salted else None, None, ref, h_ct, ln, host,
+                                  ctypes.byref(st))
+            assert rc in (0, N.GLFSX_E_CORRUPT), rc      # the bytes are arbitrary
+            row(("O", ONE_OPEN_SALTED if salted else ONE_OPEN_CLS, 1, ln),
+                aux_take(N, buf, count))
+    # two requests in one launch: a Writer's two full blocks (post_few); the
+    # index node's own launch follows and is not recorded here
+    sink = ctypes.cast(N.lib.glfsx_sink_count, N.POST_FN)
+    for bs in (16 * KIB, 16 * KIB + 16, 64 * KIB, 64 * KIB + 16, 4 * MIB):
+        data = ctypes.create_string_buffer(2 * bs)
+        counts, root = (ctypes.c_uint64 * 2)(), N.glfsx_root()
+        N.check(N.lib.glfsx_debug_aux_log(1, None, 0, None))
+        N.check(N.lib.glfsx_create(bs, bs, None, None, data, 2 * bs, sink, ctypes.byref(counts),
+                                   ctypes.byref(root)))
+        log = [r for r in aux_take(N, buf, count) if r[0] in (ONE, MED, ONE_OPEN)]
+        assert len(log) >= 2, log
+        row(("O", ONE_SMALL if bs <= 64 * KIB else ONE_MED, 2, bs), log[:1])
+    N.set_latency_wgs(old[0])
+    N.set_open_route(old[1])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("%d rows" % len(lines))
+
+
 if __name__ == "__main__":
-    main(sys.argv[1])
+    if sys.argv[1] == "--aux":
+        main_aux(sys.argv[2])
+    else:
+        main(sys.argv[1])

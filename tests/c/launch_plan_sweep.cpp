@@ -10,8 +10,18 @@
 //       G ("S family G CHACHA form" lines; the set must be kSmallGs x the
 //       dispatcher's forms; k_small_q's item arithmetic covers every blob
 //       once) and decrypt_plan ("D family form" lines; units and keystream
-//       blocks cover the bytes once, no run straddles a block).
-//   launch_plan_sweep FIXTURE         feeds every call recorded in FIXTURE
+//       blocks cover the bytes once, no run straddles a block).  Then
+//       rag_pass_recs over chunk totals 0 .. 2^21 + 1 around every multiple
+//       of 256 and around 2^20 tiles (merge totals none, one and above 2^20
+//       with each; either side of 256 and 2^20 with the totals up to 4097 and
+//       above 2^21), the five pass kinds and four latency bounds ("R family
+//       kind form" lines), and one_rec over every class, n and length on
+//       either side of 16 KiB, 64 KiB and 4 MiB ("O family QUADS salted
+//       by_value" lines): grids in closed form, refused lengths refused, and
+//       the reachable set equal to the launchable one.
+//   launch_plan_sweep --aux FIXTURE   the same replay for the ragged passes
+//       and the one-shot classes (scripts/record_launches.py --aux).
+//   launch_plan_sweep FIXTURE      feeds every call recorded in FIXTURE
 //       (scripts/record_launches.py, run at the commit before the selection
 //       moved here) to the pure functions and requires the recorded records.
 //
@@ -130,6 +140,8 @@ static Kernel kernel_of(const LaunchRec &r) {
 
 static void sweep_small();
 static void sweep_decrypt();
+static void sweep_ragged();
+static void sweep_one();
 
 static int sweep() {
   std::set<Kernel> seen;
@@ -178,6 +190,8 @@ static int sweep() {
            std::get<4>(k));
   sweep_small();
   sweep_decrypt();
+  sweep_ragged();
+  sweep_one();
   return g_failed;
 }
 
@@ -428,8 +442,183 @@ static int replay(const char *path) {
   return g_failed || lines == 0;
 }
 
+// ---- the ragged passes and the one-shot classes ----
+
+static void fail_aux(const char *what, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+  fprintf(stderr, "aux: %s: %" PRIu64 " %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", what, a, b, c, d);
+  ++g_failed;
+}
+
+using AuxKernel = std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>;
+// "R family kind form" and "O family QUADS salted by_value": the records as
+// far as they choose a kernel.
+static AuxKernel aux_kernel_of(const LaunchRec &r) {
+  if (r.family <= kLaunchRagMergeB) return AuxKernel{r.family, r.g, r.form, 0};
+  return AuxKernel{r.family, r.g, r.family == kLaunchOneOpen ? r.chacha : 0u, r.fine_div};
+}
+
+// Every record of the ten-word grid that aux_launchable accepts, as kernels.
+static std::set<AuxKernel> aux_launchable_set(uint32_t first, uint32_t last) {
+  std::set<AuxKernel> out;
+  for (uint32_t family = first; family <= last; ++family)
+    for (uint32_t g = 0; g <= 65; ++g)
+      for (uint32_t chacha = 0; chacha <= 2; ++chacha)
+        for (uint32_t aligned = 0; aligned <= 1; ++aligned)
+          for (uint32_t form = 0; form <= 3; ++form)
+            for (uint32_t by_value = 0; by_value <= 2; ++by_value) {
+              const LaunchRec r{family, g, chacha, aligned, form, 0, 1, by_value, 0, 1};
+              if (launchable(r)) out.insert(aux_kernel_of(r));
+            }
+  return out;
+}
+
+static void sweep_ragged() {
+  std::set<AuxKernel> seen;
+  // 0 .. 2^21 + 1 around every multiple of 256 chunks (m - 1, m, m + 1)
+  std::vector<uint64_t> totals = {0, 1, 2};
+  for (uint64_t m = 256; m <= (1ull << 21); m += 256)
+    for (uint64_t d : {uint64_t(0), uint64_t(1), ~uint64_t(0)}) totals.push_back(m + d);
+  // 2^20 tiles of 256 chunks, either side, and a count above 32 bits
+  for (uint64_t t : {(1ull << 28) - 256, (1ull << 28) - 255, 1ull << 28, (1ull << 28) + 1,
+                     (1ull << 32) + 5})
+    totals.push_back(t);
+  // merge totals: every value either side of 2^20 for the totals up to 4096
+  // chunks and the ones above 2^21; none, one and above 2^20 for every total
+  const std::vector<uint64_t> all_levels = {0, 1, 255, 256, (1 << 20) - 1, 1 << 20,
+                                            (1 << 20) + 1, (1 << 21) + 1};
+  const std::vector<uint64_t> few_levels = {0, 1, (1 << 20) + 1};
+  const uint32_t lats[] = {0, 1, 512, 1u << 20};
+  for (uint32_t kind = kRagPostDek; kind <= kRagOpen2; ++kind)
+    for (uint32_t lat : lats)
+      for (uint64_t chunks : totals) {
+        const bool full = chunks <= 4097 || chunks > (1ull << 21) + 1;
+        const std::vector<uint64_t> &levels = full ? all_levels : few_levels;
+        for (uint64_t a : levels)
+          for (uint64_t b : levels) {
+            const uint64_t tot[3] = {chunks, a, b};
+            const RagPlan p = rag_pass_recs(tot, kind, lat);
+            if (p.n != 1u + (a != 0) + (b != 0)) fail_aux("levels", chunks, a, b, kind);
+            uint32_t last = 0;
+            for (uint32_t i = 0; i < p.n; ++i) {
+              const LaunchRec &r = p.rec[i];
+              const uint32_t level = r.family - kLaunchRagChunk;
+              if (level > 2 || r.family <= last || !tot[level] != !r.grid)
+                fail_aux("order", chunks, a, b, kind);
+              last = r.family;
+              // the closed forms: a workgroup per tile of 256 chunks, per
+              // merge group, per large message; 2^20 at most
+              const uint64_t wgs = level ? tot[level] : (chunks + 255) >> 8;
+              if (r.grid != (wgs < (1u << 20) ? wgs : 1u << 20)) fail_aux("grid", chunks, a, b, kind);
+              if (r.form != (level == 0 && wgs > lat ? 2u : 0u)) fail_aux("form", chunks, a, b, lat);
+              if (r.g != kind || r.chacha != (kind == kRagPostCid || kind >= kRagOpen1) ||
+                  r.items != log_word(tot[level]) || r.aligned || r.split_log2 || r.fine_div || r.n)
+                fail_aux("record", chunks, a, b, kind);
+              if (chunks && !launchable(r)) fail_aux("not launchable", chunks, a, b, kind);
+              if (r.grid) seen.insert(aux_kernel_of(r));
+            }
+          }
+      }
+  if (seen != aux_launchable_set(kLaunchRagChunk, kLaunchRagMergeB)) {
+    fprintf(stderr, "ragged: the reachable and the launchable set differ\n");
+    ++g_failed;
+  }
+  for (const AuxKernel &k : seen)
+    printf("R %u %u %u\n", std::get<0>(k), std::get<1>(k), std::get<2>(k));
+}
+
+static void sweep_one() {
+  std::set<AuxKernel> seen;
+  const uint64_t MiB = 1 << 20;
+  const uint64_t lens[] = {0, 1, 16383, 16384, 16385, 65535, 65536, 65537, 4 * MiB, 4 * MiB + 1};
+  for (int c = 0; c < kOneClasses; ++c)
+    for (uint32_t n : {0u, 1u, 2u, 1024u})
+      for (uint64_t len : lens) {
+        LaunchRec r;
+        const bool ok = one_rec(OneClass(c), n, len, &r);
+        const bool med = c == kOneMed;
+        // what the ladders refused: above the class's limit; at or below
+        // kMaxOneLen for the medium class; nothing when there is no request
+        const bool want = n == 0 || (med ? len > kMaxOneLen && len <= kMaxMedLen : len <= kMaxOneLen);
+        if (ok != want) fail_aux("refusal", c, n, len, ok);
+        if (!ok || n == 0) {
+          if (r.grid || r.family) fail_aux("a record without a launch", c, n, len, ok);
+          continue;
+        }
+        const uint32_t family = med ? kLaunchMed : c == kOneSmall ? kLaunchOne : kLaunchOneOpen;
+        const uint32_t quads = len <= 16384 ? 16 : 64, wmax = med ? uint32_t((len + 65535) >> 16) : 1;
+        const uint32_t salted = c == kOneOpenSalted, trees = salted ? 2 : 1;
+        if (r.family != family || r.g != quads || r.chacha != (c == kOneOpen ? 0u : 1u) ||
+            r.aligned != 1 || r.form || r.split_log2 || r.grid != n * wmax ||
+            r.fine_div != (n == 1) || r.items != len || r.n != n)
+          fail_aux("record", c, n, len, r.grid);
+        if (one_block(r) != quads * 4 * trees) fail_aux("block", c, n, len, one_block(r));
+        if (!launchable(r)) fail_aux("not launchable", c, n, len, 0);
+        seen.insert(aux_kernel_of(r));
+      }
+  if (seen != aux_launchable_set(kLaunchOne, kLaunchOneOpen)) {
+    fprintf(stderr, "one-shot: the reachable and the launchable set differ\n");
+    ++g_failed;
+  }
+  for (const AuxKernel &k : seen)
+    printf("O %u %u %u %u\n", std::get<0>(k), std::get<1>(k), std::get<2>(k), std::get<3>(k));
+}
+
+// launch_plan_sweep --aux FIXTURE: the rows of scripts/record_launches.py
+// --aux (recorded from the launchers as they were before rag_pass_recs and
+// one_rec) against those two functions.
+//   R chunks groups large kind latency_wgs nrec <records>
+//   O class n max_len nrec <records>
+static int replay_aux(const char *path) {
+  FILE *f = fopen(path, "r");
+  if (!f) {
+    fprintf(stderr, "cannot open %s\n", path);
+    return 1;
+  }
+  size_t lines = 0;
+  char tag[4];
+  while (fscanf(f, "%3s", tag) == 1) {
+    uint64_t in[5] = {0, 0, 0, 0, 0}, nrec = 0;
+    const int nin = tag[0] == 'R' ? 5 : 3;
+    bool ok = (tag[0] == 'R' || tag[0] == 'O') && tag[1] == 0;
+    for (int i = 0; ok && i < nin; ++i) ok = fscanf(f, "%" SCNu64, &in[i]) == 1;
+    ok = ok && fscanf(f, "%" SCNu64, &nrec) == 1 && nrec <= 3;
+    std::vector<LaunchRec> want(ok ? nrec : 0);
+    for (LaunchRec &r : want) {
+      uint32_t *w = &r.family;
+      for (size_t i = 0; ok && i < kLaunchRecWords; ++i) ok = fscanf(f, "%" SCNu32, &w[i]) == 1;
+    }
+    if (!ok) {
+      fprintf(stderr, "%s: malformed line %zu\n", path, lines + 1);
+      fclose(f);
+      return 1;
+    }
+    std::vector<LaunchRec> have;
+    if (tag[0] == 'R') {
+      const RagPlan p = rag_pass_recs(in, uint32_t(in[3]), uint32_t(in[4]));
+      have.assign(p.rec, p.rec + p.n);
+    } else {
+      LaunchRec r;
+      if (!one_rec(OneClass(in[0]), uint32_t(in[1]), in[2], &r)) fail_aux("refused", in[0], in[1], in[2], 0);
+      if (r.grid) have.push_back(r);
+    }
+    if (have.size() != want.size() ||
+        memcmp(have.data(), want.data(), have.size() * sizeof(LaunchRec)) != 0) {
+      fail_aux("differs from the recorded launches", lines + 1, in[0], in[1], in[2]);
+      for (const LaunchRec &r : have)
+        fprintf(stderr, "  now %u %u %u %u %u %u %u %u %u %u\n", r.family, r.g, r.chacha, r.aligned,
+                r.form, r.split_log2, r.grid, r.fine_div, r.items, r.n);
+    }
+    ++lines;
+  }
+  fclose(f);
+  printf("replayed %zu\n", lines);
+  return g_failed || lines == 0;
+}
+
 int main(int argc, char **argv) {
-  const int bad = argc > 1 ? replay(argv[1]) : sweep();
+  const int bad = argc > 2 && !strcmp(argv[1], "--aux") ? replay_aux(argv[2])
+                  : argc > 1                             ? replay(argv[1])
+                                                         : sweep();
   if (bad) {
     fprintf(stderr, "launch_plan_sweep: failed\n");
     return 1;

@@ -1,8 +1,9 @@
-"""One-shot posts (launch_one / k_one): a message of at most 64 KiB posted in
-one launch straight from pinned staging; up to 4 MiB in two launches over
-64 KiB spans (launch_med: k_med_dek / k_med_cid, last-arriving workgroup
-merges); concurrent callers coalesced into shared launches (oneshot.cpp
-one_post_many).  Every ref and ctext == the oracle's
+"""One-shot posts (launch_one_class / k_one): a message of at most 64 KiB
+posted in one launch straight from pinned staging; up to 4 MiB in two launches
+over 64 KiB spans (the medium pair k_med_dek / k_med_cid, last-arriving
+workgroup merges); concurrent callers coalesced into shared launches
+(oneshot.cpp one_post_many).  The edge tests first assert from the aux log
+which instantiation ran.  Every ref and ctext == the oracle's
 ref.go:98 post(); Writers whose tail blocks and index nodes take this route
 (block sizes <= 4 MiB) == the oracle Writer (blob.go:85-206), Post order
 included."""
@@ -12,6 +13,9 @@ import random
 import threading
 
 import pytest
+
+from test_gpu_small_decrypt_matrix import (MED, ONE, ONE_FAMILIES, aux_reset, aux_take,
+                                           one_expect)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +39,13 @@ def test_one_shot_post_edges(gpu, O, keyed):
         salt = rng.randbytes(32)
         key = rng.randbytes(32) if keyed else None
         data = rng.randbytes(n)
-        assert _gpu_post(gpu, salt, data, key) == O.post(salt, data, key), n
+        aux_reset(gpu)
+        got = _gpu_post(gpu, salt, data, key)
+        # one request: k_one_v, QUADS 16 up to 16 KiB and 64 above
+        log = aux_take(gpu, families=ONE_FAMILIES)
+        assert log == [one_expect(ONE, 1, n)], n
+        assert (log[0][1], log[0][7]) == (16 if n <= 16384 else 64, 1), n
+        assert got == O.post(salt, data, key), n
 
 
 @pytest.mark.parametrize("keyed", [False, True])
@@ -47,7 +57,13 @@ def test_medium_post_edges(gpu, O, keyed):
         salt = rng.randbytes(32)
         key = rng.randbytes(32) if keyed else None
         data = rng.randbytes(n)
-        assert _gpu_post(gpu, salt, data, key) == O.post(salt, data, key), n
+        aux_reset(gpu)
+        got = _gpu_post(gpu, salt, data, key)
+        # the by-value medium pair, a workgroup per 64 KiB span
+        log = aux_take(gpu, families=ONE_FAMILIES)
+        assert log == [one_expect(MED, 1, n)], n
+        assert (log[0][6], log[0][7]) == (-(-n // 65536), 1), n
+        assert got == O.post(salt, data, key), n
 
 
 def test_one_shot_post_unaligned_source(gpu, O):
@@ -62,16 +78,21 @@ def test_one_shot_post_unaligned_source(gpu, O):
 
 
 @pytest.mark.parametrize("keyed", [False, True])
-@pytest.mark.parametrize("bs", [1024, 4096, 65536, 1 << 20, 4 << 20])
+@pytest.mark.parametrize("bs", [1024, 4096, 16400, 65536, 1 << 20, 4 << 20])
 def test_writer_small_blocks_one_shot(gpu, O, bs, keyed):
     """Tail blocks and every index node (bs <= 4 MiB) go through one-shot
     posts (index nodes from their refs alone, the rest read as zero): roots
-    and the full Post log (kind, ref, ctext) == the oracle."""
+    and the full Post log (kind, ref, ctext) == the oracle.  A Finish with
+    one to eight staged blocks posts them and the tail in one call (post_few):
+    two or more requests of a class go through the descriptor array -- k_one<16>
+    up to 16 KiB blocks, k_one<64> above (16400: the smallest block size above
+    the boundary that is a multiple of 16), the medium pair from 1 MiB."""
     from glfs_amd import bigblob
     rng = random.Random(bs)
     sizes = [0, 1, bs - 1, bs, bs + 1, 3 * bs + 5]
     if bs <= 65536:
         sizes.append((bs // 64 + 2) * bs + 17)  # a full index node, then a second level
+    arrays = set()
     for size in sizes:
         data = rng.randbytes(size)
         salt = rng.randbytes(32)
@@ -80,13 +101,28 @@ def test_writer_small_blocks_one_shot(gpu, O, bs, keyed):
         st = bigblob.MemStore(bs)
         w = bigblob.Machine(bs).new_writer(st, salt, key)
         w.write(data)
+        aux_reset(gpu)
         root = w.finish()
+        log = aux_take(gpu, families=ONE_FAMILIES)
+        full, tail = divmod(size, bs)
+        if 1 <= full <= 8:
+            # post_few's launches come first: the small class, then the medium
+            # one; the index node's own posts follow
+            k = full + (tail > 0)
+            if bs <= 65536:
+                want_log = [one_expect(ONE, k, bs)]
+            else:
+                want_log = ([one_expect(ONE, 1, tail)] if tail else []) + [one_expect(MED, full, bs)]
+            assert log[:len(want_log)] == want_log, (bs, size, log)
+            arrays |= {(r[0], r[1]) for r in want_log if r[7] == 0}
         w.close()
         assert root.ref.marshal_binary() == want_root, (bs, size)
         assert [(k, r, n) for k, r, n in st.log] == \
                [(k, r, n) for k, r, n, _ in want_posts], (bs, size)
         for _, r, _, c in want_posts:
             assert st.blobs[r[:32]] == c, (bs, size)
+    # the array form of this block size's class ran (sizes bs + 1 and 3 bs + 5)
+    assert arrays == {(MED, 64) if bs > 65536 else (ONE, 16 if bs <= 16384 else 64)}
 
 
 def test_concurrent_one_shot_posts(gpu, O):

@@ -10,6 +10,9 @@ import threading
 
 import pytest
 
+from test_gpu_small_decrypt_matrix import (MED, ONE, ONE_FAMILIES, ONE_OPEN, aux_key,
+                                           aux_kernel_table, aux_reset, aux_take, one_expect)
+
 pytestmark = pytest.mark.gpu
 
 MiB = 1 << 20
@@ -63,12 +66,18 @@ def _call(N, ct, ref, salt, cid_key, want=True, inplace=False, off=0):
 
 
 def _both(N, *a, **kw):
-    """The call under route 1 and under route 2: identical results."""
+    """The call under route 1 and under route 2: identical results.  Route 2
+    up to 64 KiB is one k_one_open_v launch, which the aux log must show."""
     out = []
     try:
         for route in (1, 2):
             N.set_open_route(route)
+            aux_reset(N)
             out.append(_call(N, *a, **kw))
+            log = aux_take(N, families=ONE_FAMILIES)
+            n, salted = len(a[0]), a[2] is not None
+            assert log == ([one_expect(ONE_OPEN, 1, n, salted)] if route == 2 and n <= 65536
+                           else []), (route, n, salted, log)
     finally:
         N.set_open_route(0)
     assert out[0][:4] == out[1][:4], "the staged route and the one-shot kernel disagree"
@@ -88,6 +97,8 @@ def test_clean(gpu, O, n):
     for keyed in (False, True):
         data, ref, ct = _msg(n, keyed)
         for salt in (SALT, None):
+            # (route 2, n <= 64 KiB: _both has seen k_one_open_v<16 up to 16 KiB
+            # else 64, salted or not> in the aux log)
             rc, st, pt, guard, _ = _both(gpu, ct, ref, salt, CID_KEY if keyed else None)
             assert (rc, st) == (0, 0), (n, keyed, salt is not None)   # the poison is gone
             assert pt == data
@@ -199,7 +210,11 @@ def test_posts_and_opens_share_launches(gpu, O):
     """16 threads, each 50 calls alternating glfsx_post and glfsx_open on
     distinct messages of mixed small sizes: every ref, ciphertext, plaintext
     and status is the oracle's, and the calls went out as launches of the
-    coalescing poster."""
+    coalescing poster.  Every launch logged is in the table of the one-shot
+    instantiations and carries at least one request per workgroup class; which
+    array-form k_one_open kernels the run reached is printed, not asserted:
+    whether two opens coalesce is a matter of thread timing, and no entry
+    point opens several blocks in one call."""
     T, K = 16, 50
     sizes = [0, 1, 100, 1024, 4097, 16384, 16385, 20000, 40000, 65536, 333, 8191]
     work = []
@@ -243,14 +258,27 @@ def test_posts_and_opens_share_launches(gpu, O):
 
     gpu.set_open_route(0)
     gpu.lib.glfsx_one_stats(1, out)
+    aux_reset(gpu)
     threads = [threading.Thread(target=run, args=(w,)) for w in work]
     for th in threads:
         th.start()
     for th in threads:
         th.join()
     assert not errors, errors[0]
+    log = aux_take(gpu, cap=4096, families=ONE_FAMILIES)
+    table = aux_kernel_table()
+    known = set().union(*(keys for keys, _ in table.values()))
+    assert log and all(aux_key(r) in known for r in log)
+    for r in log:
+        # n requests, none above 64 KiB; one goes by value, more as an array
+        assert r[0] in (ONE, ONE_OPEN)
+        assert r == one_expect(r[0], r[9], r[8], salted=r[2]), r
+    reached = sorted(name for name, (keys, _) in table.items()
+                     if name.startswith("k_one_open<") and keys & {aux_key(r) for r in log})
+    print("array-form k_one_open instantiations reached:", reached or "none")
     gpu.lib.glfsx_one_stats(1, out)
     launches, requests = out[0], out[1]
     # 25 posts and 25 + 25 opens per thread, every one through the poster
     assert requests == T * (K // 2) * 3
     assert 0 < launches <= requests
+    assert sum(r[9] for r in log) == requests and len(log) >= launches

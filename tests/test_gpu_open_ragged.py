@@ -9,6 +9,10 @@ import random
 import numpy as np
 import pytest
 
+from test_gpu_small_decrypt_matrix import (OPEN0, OPEN1, OPEN2, RAG_CHUNK, RAG_FAMILIES,
+                                           RAG_MERGE_A, RAG_MERGE_B, aux_reset, aux_take,
+                                           latency_wgs_now, rag_expect)
+
 pytestmark = pytest.mark.gpu
 
 KIB, MIB = 1 << 10, 1 << 20
@@ -68,9 +72,12 @@ def _dev(torch, b):
 
 
 def _launch(N, torch, d_ct, offs, lens, max_len, refs, ptext="separate", salt=SALT, key=None,
-            stream=None):
+            stream=None, thr=False):
     """One call; returns the device tensors (status, ptext or None) without
-    synchronising anything itself."""
+    synchronising anything itself.  thr (None: the default latency threshold,
+    else its value): the aux log must show the one pass in the call's mode --
+    2 with a salt, else 1 with a plaintext buffer, else 0 -- in the ARX form
+    of that threshold, and the merge levels the lengths have work for."""
     n = len(lens)
     do = torch.tensor(offs, dtype=torch.int64, device="cuda")
     dl = torch.tensor(lens, dtype=torch.int64, device="cuda")
@@ -80,11 +87,22 @@ def _launch(N, torch, d_ct, offs, lens, max_len, refs, ptext="separate", salt=SA
     if ptext == "separate":
         pt = torch.full_like(d_ct, PT_FILL)
     torch.cuda.synchronize()
+    aux_reset(N)
     rc = N.lib.glfsx_open_ragged_device(
         salt, key, d_ct.data_ptr(), do.data_ptr(), dl.data_ptr(), n, max_len,
         d_refs.data_ptr(), pt.data_ptr() if pt is not None else None, st.data_ptr(),
         stream.cuda_stream if stream is not None else None)
     assert rc == 0, N.last_error()
+    if thr is not False:
+        kind = OPEN2 if salt is not None else OPEN1 if pt is not None else OPEN0
+        form = 0 if thr is None else 2
+        log = aux_take(N, families=RAG_FAMILIES)
+        sel = [ln for ln in lens if ln <= max_len]
+        assert thr is None or latency_wgs_now(N) == thr
+        assert log == rag_expect(sel, kind, latency_wgs_now(N)), (kind, thr)
+        if max(sel) > 256 * KIB:
+            assert [(r[0], r[1], r[4]) for r in log] == [
+                (RAG_CHUNK, kind, form), (RAG_MERGE_A, kind, 0), (RAG_MERGE_B, kind, 0)]
     return st, pt, (do, dl, d_refs)
 
 
@@ -99,14 +117,15 @@ def _same(got, want, what):
 
 
 def _run(N, O, name, lens, seed, offs, total, ptext="separate", key=None, salt=SALT,
-         stream=None, want=None):
+         stream=None, want=None, thr=False):
     """A clean batch in one ptext mode: every status 0 (or `want`), the
     plaintext the messages, every other byte of every buffer its fill."""
     import torch
     msgs, refs, cts = _batch(O, name, lens, seed, key)
     ct_img = _image(total, offs, cts, GAP)
     d_ct = torch.from_numpy(ct_img.copy()).cuda()
-    st, pt, _keep = _launch(N, torch, d_ct, offs, lens, max(lens), refs, ptext, salt, key, stream)
+    st, pt, _keep = _launch(N, torch, d_ct, offs, lens, max(lens), refs, ptext, salt, key, stream,
+                            thr)
     got = _status(torch, st)
     assert got == (want if want is not None else [0] * len(lens)), \
         [(i, s) for i, s in enumerate(got) if s][:10]
@@ -148,7 +167,7 @@ def test_edge_lengths(gpu, O, latency_wgs, align, phase, thr):
     lens = _edge_order()
     offs, total = _offsets(lens, align, phase, gap=3)
     for ptext in ("separate", "inplace", "none"):
-        _run(gpu, O, "edge", lens, 21, offs, total, ptext=ptext)
+        _run(gpu, O, "edge", lens, 21, offs, total, ptext=ptext, thr=thr)      # mode 2
 
 
 def test_keyed_cid_and_no_salt(gpu, O):
@@ -157,9 +176,9 @@ def test_keyed_cid_and_no_salt(gpu, O):
     lens = _edge_order()
     offs, total = _offsets(lens, 16, 0, gap=5)
     for ptext in ("separate", "inplace", "none"):
-        _run(gpu, O, "edge", lens, 21, offs, total, ptext=ptext, key=CID_KEY)
-        _run(gpu, O, "edge", lens, 21, offs, total, ptext=ptext, key=CID_KEY, salt=None)
-        _run(gpu, O, "edge", lens, 21, offs, total, ptext=ptext, salt=None)
+        _run(gpu, O, "edge", lens, 21, offs, total, ptext=ptext, key=CID_KEY, thr=None)
+        _run(gpu, O, "edge", lens, 21, offs, total, ptext=ptext, key=CID_KEY, salt=None, thr=None)
+        _run(gpu, O, "edge", lens, 21, offs, total, ptext=ptext, salt=None, thr=None)
     # the wrong CID key: bit 0 everywhere, the DEK check still passes
     import torch
     msgs, refs, cts = _batch(O, "edge", lens, 21, CID_KEY)
@@ -210,10 +229,12 @@ def test_damage(gpu, O, latency_wgs, thr):
     ct_img = _image(total, offs, cts, GAP)
     for ptext in ("separate", "none"):
         d_ct = torch.from_numpy(ct_img.copy()).cuda()
-        st, _pt, _k = _launch(gpu, torch, d_ct, offs, lens, max(lens), refs, ptext)
+        st, _pt, _k = _launch(gpu, torch, d_ct, offs, lens, max(lens), refs, ptext, thr=thr)
         assert _status(torch, st) == want
-        # no salt: only bit 0, where the CID is wrong
-        st, _pt, _k = _launch(gpu, torch, d_ct, offs, lens, max(lens), refs, ptext, salt=None)
+        # no salt: only bit 0, where the CID is wrong (mode 1 with a plaintext
+        # buffer, mode 0 without: both ARX forms of each over the two thr)
+        st, _pt, _k = _launch(gpu, torch, d_ct, offs, lens, max(lens), refs, ptext, salt=None,
+                              thr=thr)
         assert _status(torch, st) == [w & 1 for w in want]
     # a foreign salt: bit 1 on every message, the empty one included
     st, _pt, _k = _launch(gpu, torch, d_ct, offs, lens, max(lens), refs, "none", salt=FOREIGN)

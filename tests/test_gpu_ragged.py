@@ -10,6 +10,10 @@ import random
 import numpy as np
 import pytest
 
+from test_gpu_small_decrypt_matrix import (POST_CID, POST_DEK, RAG_CHUNK, RAG_FAMILIES,
+                                           RAG_MERGE_A, RAG_MERGE_B, aux_reset, aux_take,
+                                           latency_wgs_now, rag_expect)
+
 pytestmark = pytest.mark.gpu
 
 KIB, MIB = 1 << 10, 1 << 20
@@ -125,12 +129,26 @@ def test_edge_lengths(gpu, O, latency_wgs, align, phase, thr):
     """Chunk counts 1 .. 5121 on both sides of the wave (64), merge-group
     (256) and level-B boundaries, at 64-B aligned, 16-B aligned and odd
     offsets, in the compiler's ARX form (default threshold) and the asm form
-    (threshold 0)."""
+    (threshold 0).  The aux log says which k_rag_chunk ran in each pass and
+    that both merge levels did."""
     if thr is not None:
         latency_wgs(thr)
     lens = _edge_order()
     offs, total = _offsets(lens, align, phase, gap=3)
+    aux_reset(gpu)
     _run(gpu, O, "edge", lens, 21, offs, total)
+    log = aux_take(gpu, families=RAG_FAMILIES)
+    # the DEK pass, then the CID pass: chunks, level A (a message of more than
+    # one chunk), level B (one of more than 256)
+    assert max(lens) > 256 * KIB
+    assert [(r[0], r[1], r[4]) for r in log] == [
+        (family, kind, form if family == RAG_CHUNK else 0)
+        for kind in (POST_DEK, POST_CID)
+        for form in ((0,) if thr is None else (2,))
+        for family in (RAG_CHUNK, RAG_MERGE_A, RAG_MERGE_B)]
+    lat = latency_wgs_now(gpu)      # the default, or thr
+    assert thr is None or lat == thr
+    assert log == rag_expect(lens, POST_DEK, lat) + rag_expect(lens, POST_CID, lat)
 
 
 def test_keyed_cid_no_ctext_in_place(gpu, O):

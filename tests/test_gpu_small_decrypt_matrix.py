@@ -23,10 +23,21 @@ so no row asks for it.
 
 Decrypt (glfsx_decrypt_batch_device): the input is the oracle's post of the
 splitmix stream, so the expected plaintext does not come from the library.
+
+The same log holds the levels of the ragged passes and the one-shot classes.
+Their 32 instantiations are asserted in the tests that already have their
+shapes (test_gpu_ragged, test_gpu_open_ragged, test_gpu_one,
+test_gpu_one_open), with rag_expect and one_expect below; aux_kernel_table
+names each instantiation, the records that mean it ran and that test, and
+test_aux_table_covers_the_reachable_set holds the table against
+launch_plan.h ("R" and "O" lines of the sweep program) and replays
+tests/golden/aux_launch_records.txt.  A call may now log families beside the
+ones a test is about, so every comparison selects its own (aux_take).
 """
 import collections
 import ctypes
 import functools
+import os
 import random
 import re
 
@@ -39,6 +50,10 @@ from test_gpu_pass_matrix import knobs, sweep_program  # noqa: F401  (fixtures, 
 
 GIB = 1 << 30
 SMALL, SMALL_Q, LINES, DECRYPT = 5, 6, 7, 8   # GLFSX_LOG_* (include/glfsx.h)
+RAG_CHUNK, RAG_MERGE_A, RAG_MERGE_B, ONE, MED, ONE_OPEN = 9, 10, 11, 12, 13, 14
+SMALL_FAMILIES, DEC_FAMILIES = (SMALL, SMALL_Q), (LINES, DECRYPT)
+RAG_FAMILIES, ONE_FAMILIES = (RAG_CHUNK, RAG_MERGE_A, RAG_MERGE_B), (ONE, MED, ONE_OPEN)
+POST_DEK, POST_CID, OPEN0, OPEN1, OPEN2 = range(5)   # RagKind (launch_plan.h)
 SMALL_GS = (1, 2, 4, 8, 16)
 BS = 2 * MIB                                  # the blobs' block size
 FINE_DIV = 8                                  # kSmallFineDiv (launch_plan.h)
@@ -124,7 +139,132 @@ def table_kernels():
     return small, dec
 
 
+# ---------------------------------- the ragged passes and the one-shot classes
+# These 32 instantiations are asserted where their shapes already are: each
+# test below resets the aux log, makes its call, and compares the records with
+# rag_expect / one_expect before it compares bytes with the oracle.
+def rag_totals(lens):
+    """The plan's totals over the selected messages: chunks, merge groups,
+    messages of more than 256 chunks (ragged_kernels.h k_rag_count)."""
+    c = [max(1, -(-ln // 1024)) for ln in lens]
+    return sum(c), sum(-(-x // 256) for x in c if x > 1), sum(x > 256 for x in c)
+
+
+def latency_wgs_now(N):
+    """The latency threshold in force (the setter returns the previous value)."""
+    v = N.set_latency_wgs(0)
+    N.set_latency_wgs(v)
+    return v
+
+
+def rag_expect(lens, kind, latency_wgs):
+    """One ragged pass over messages of these lengths: the chunk level (form 0
+    when its tiles of 256 chunks number at most latency_wgs, else 2), merge
+    level A exactly when a message has more than one chunk, B when more than
+    256."""
+    return rag_expect_totals(rag_totals(lens), kind, latency_wgs)
+
+
+def rag_expect_totals(tot, kind, latency_wgs):
+    tiles = -(-tot[0] // 256)
+    chacha = kind == POST_CID or kind >= OPEN1
+    out = [rec(RAG_CHUNK, kind, chacha, 0, 0 if tiles <= latency_wgs else 2, 0,
+               min(tiles, 1 << 20), 0, tot[0], 0)]
+    for family, total in ((RAG_MERGE_A, tot[1]), (RAG_MERGE_B, tot[2])):
+        if total:
+            out.append(rec(family, kind, chacha, 0, 0, 0, min(total, 1 << 20), 0, total, 0))
+    return out
+
+
+def one_expect(family, n, max_len, salted=True):
+    """One one-shot class launch: QUADS 16 up to 16 KiB, else 64 (the medium
+    pair 64, a workgroup per 64 KiB); word 7 is 1 when the one descriptor went
+    by value."""
+    quads = 16 if max_len <= 16384 else 64
+    wmax = -(-max_len // 65536) if family == MED else 1
+    return rec(family, quads, salted if family == ONE_OPEN else 1, 1, 0, 0, n * wmax,
+               int(n == 1), max_len, n)
+
+
+T_RAG = "test_gpu_ragged.py::test_edge_lengths"
+T_ORAG = "test_gpu_open_ragged.py::test_edge_lengths"
+T_ORAG_01 = "test_gpu_open_ragged.py::test_damage"
+T_ONE = "test_gpu_one.py::test_one_shot_post_edges"
+T_MED = "test_gpu_one.py::test_medium_post_edges"
+T_WRITER = "test_gpu_one.py::test_writer_small_blocks_one_shot"
+T_OPEN = "test_gpu_one_open.py::test_clean"
+T_SHARED = "test_gpu_one_open.py::test_posts_and_opens_share_launches"
+
+
+def aux_kernel_table():
+    """Instantiation -> (the record keys that mean it ran, as launch_plan_sweep
+    prints them: family, kind, form / family, QUADS, salted, by value; the
+    test that asserts them)."""
+    t = {}
+    for kind, name in ((POST_DEK, "false"), (POST_CID, "true")):
+        for form in (0, 2):
+            t["k_rag_chunk<%s, %d>" % (name, form)] = ({(RAG_CHUNK, kind, form)}, T_RAG)
+    t["k_rag_merge_a"] = ({(RAG_MERGE_A, POST_DEK, 0), (RAG_MERGE_A, POST_CID, 0)}, T_RAG)
+    t["k_rag_merge_b"] = ({(RAG_MERGE_B, POST_DEK, 0), (RAG_MERGE_B, POST_CID, 0)}, T_RAG)
+    for mode, where in ((0, T_ORAG_01), (1, T_ORAG_01), (2, T_ORAG)):
+        for form in (0, 2):
+            t["k_rag_open_chunk<%d, %d>" % (mode, form)] = ({(RAG_CHUNK, OPEN0 + mode, form)}, where)
+    for level, family in (("a", RAG_MERGE_A), ("b", RAG_MERGE_B)):
+        t["k_rag_open_merge_%s<false>" % level] = ({(family, OPEN0, 0), (family, OPEN1, 0)},
+                                                   T_ORAG_01)
+        t["k_rag_open_merge_%s<true>" % level] = ({(family, OPEN2, 0)}, T_ORAG)
+    for q in (16, 64):
+        t["k_one_v<%d>" % q] = ({(ONE, q, 0, 1)}, T_ONE)
+        t["k_one<%d>" % q] = ({(ONE, q, 0, 0)}, T_WRITER)
+        for salted in (0, 1):
+            name = "%d, %s>" % (q, "true" if salted else "false")
+            t["k_one_open_v<" + name] = ({(ONE_OPEN, q, salted, 1)}, T_OPEN)
+            # reached only when concurrent callers coalesce (DESIGN.md section 2)
+            t["k_one_open<" + name] = ({(ONE_OPEN, q, salted, 0)}, T_SHARED)
+    for half in ("dek", "cid"):     # one record for the pair
+        t["k_med_%s_v" % half] = ({(MED, 64, 0, 1)}, T_MED)
+        t["k_med_%s" % half] = ({(MED, 64, 0, 0)}, T_WRITER)
+    return t
+
+
+def aux_key(r):
+    """The table's key of a logged record."""
+    if r[0] in RAG_FAMILIES:
+        return (r[0], r[1], r[4])
+    return (r[0], r[1], r[2] if r[0] == ONE_OPEN else 0, r[7])
+
+
 # ------------------------------------------------------------- CPU meta-tests
+def test_aux_table_covers_the_reachable_set(sweep_program):
+    """The 32 instantiations of the ragged and one-shot families: the table's
+    record keys are exactly what rag_pass_recs and one_rec can return (the
+    program itself fails unless that is the launchable set), and the pure
+    functions reproduce the launches recorded from the old launchers."""
+    lines = [ln.split() for ln in _run([sweep_program]).splitlines()]
+    want = {tuple(int(x) for x in ln[1:]) for ln in lines if ln[0] in ("R", "O")}
+    table = aux_kernel_table()
+    have = set().union(*(keys for keys, _ in table.values()))
+    assert have == want, (sorted(want - have), sorted(have - want))
+    assert len(table) == 32 and len(want) == 34
+    fixture = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                           "aux_launch_records.txt")
+    n = sum(1 for _ in open(fixture))
+    assert n >= 150
+    assert "replayed %d\n" % n in _run([sweep_program, "--aux", fixture])
+    # the helpers the GPU tests assert with agree with the fixture's rows
+    for ln in open(fixture):
+        w = ln.split()
+        if w[0] == "R":
+            tot, kind, lat = tuple(int(x) for x in w[1:4]), int(w[4]), int(w[5])
+            recs = [tuple(int(x) for x in w[7 + 10 * i:17 + 10 * i]) for i in range(int(w[6]))]
+            assert recs == rag_expect_totals(tot, kind, lat)
+        else:
+            cls, cnt, max_len = (int(x) for x in w[1:4])
+            got = tuple(int(x) for x in w[5:15])
+            family = (ONE, MED, ONE_OPEN, ONE_OPEN)[cls]
+            assert got == one_expect(family, cnt, max_len, salted=cls == 3)
+
+
 def test_tables_cover_the_reachable_sets(sweep_program):
     lines = [ln.split() for ln in _run([sweep_program]).splitlines()]
     want_small = {tuple(int(x) for x in ln[1:]) for ln in lines if ln[0] == "S"}
@@ -150,12 +290,15 @@ def aux_reset(N):
     N.check(N.lib.glfsx_debug_aux_log(1, None, 0, None))
 
 
-def aux_take(N, cap=64):
+def aux_take(N, cap=64, families=None):
+    """The aux log since the last reset, emptied; `families`: only the records
+    of the families a test is about (a call may launch others beside them)."""
     buf = (ctypes.c_uint32 * (LOG_WORDS * cap))()
     n = ctypes.c_size_t()
     N.check(N.lib.glfsx_debug_aux_log(1, buf, cap, ctypes.byref(n)))
     assert n.value <= cap, n.value
-    return [tuple(buf[i * LOG_WORDS:(i + 1) * LOG_WORDS]) for i in range(n.value)]
+    log = [tuple(buf[i * LOG_WORDS:(i + 1) * LOG_WORDS]) for i in range(n.value)]
+    return [r for r in log if families is None or r[0] in families]
 
 
 def poisoned(torch, n):
@@ -308,7 +451,7 @@ def test_small(gpu, O, knobs, g, queue):
             sd.d_offs.data_ptr(), sd.d_lens.data_ptr(), n, g * KIB,
             ct.data_ptr() + off + 64 if ct is not None else None, roots.data_ptr(), None))
         torch.cuda.synchronize()
-        assert aux_take(N) == expect, what
+        assert aux_take(N, families=SMALL_FAMILIES) == expect, what
         assert_same(torch, roots, sd.want_roots[variant == "keyed"], what + " roots")
         if ct is not None:
             assert_same(torch, ct[off:], sd.want_ct, what + " ctext")
@@ -356,7 +499,7 @@ def test_small_queue_loop(gpu, O, ln):
                                               offs.data_ptr(), lens.data_ptr(), n, ln,
                                               ct.data_ptr() + 64, roots.data_ptr(), None))
         torch.cuda.synchronize()
-        log = aux_take(N)
+        log = aux_take(N, families=SMALL_FAMILIES)
         print("k_small_q ln=%d run %d:" % (ln, run), log)
         assert len(log) == 2
         for ch, r in enumerate(log):
@@ -427,7 +570,7 @@ def test_small_offsets_above_2_and_4_gib(gpu, O, knobs, queue):
                                           ct.data_ptr(), roots.data_ptr(), None))
     torch.cuda.synchronize()
     expect = small_expect(4, queue, n)
-    assert aux_take(N) == expect
+    assert aux_take(N, families=SMALL_FAMILIES) == expect
     if queue:
         assert expect[0][7] == 4      # the last group runs as fine items
     assert_same(torch, roots, to_dev(torch, want_roots + bytes([POISON]) * 64), "roots")
@@ -549,7 +692,7 @@ def test_decrypt(gpu, O, knobs, row):
         N.check(N.lib.glfsx_decrypt_batch_device(d_ct.data_ptr() + a, total, row.bs,
                                                  d_refs.data_ptr(), out.data_ptr() + b, None))
         torch.cuda.synchronize()
-        assert aux_take(N) == dec_expect(row, form), what
+        assert aux_take(N, families=DEC_FAMILIES) == dec_expect(row, form), what
         assert_same(torch, out, want, what)
         assert_same(torch, d_ct, d_ct0, what + " ctext")
 
@@ -579,7 +722,7 @@ def test_decrypt_runs_loop(gpu, O, knobs, row):
         N.check(N.lib.glfsx_decrypt_batch_device(d_ct.data_ptr(), total, row.bs,
                                                  d_refs.data_ptr(), out.data_ptr() + 64, None))
         torch.cuda.synchronize()
-        log = aux_take(N)
+        log = aux_take(N, families=DEC_FAMILIES)
         assert log == dec_expect(row, form, row.run_shift, 16384), what
         lines = log[0]
         assert lines[5] == row.run_shift and lines[7] == row.upb_shift, what
